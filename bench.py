@@ -13,6 +13,10 @@ region starts. Weights: seeded synthetic GAR-1B (no checkpoint is reachable offl
 One JSON line on rank 0 (see DESIGN.md "Measurement"): value = N*K*B / max-over-ranks wall time; `roofline` = the
 dominant kernel (bf16 tile GEMM: ViT + projector + prefill) timed live with HIP events on the launch stream over the
 timed region; `cpu_baseline` = the fp32 CPU oracle on a bounded sample of the same workload on this box's cores.
+`ms_per_step` = milliseconds of one of the K timed steps.
+
+`--dump-outputs DIR` writes what the last timed step returned (the caption ids gathered on rank 0) as DIR/sequences.npy;
+the inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -100,7 +104,15 @@ def parse(argv=None):
     ap.add_argument("--eos-mix-poll", type=int, default=8, help="--eos-mix: decode steps between two polls of the finished latches")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0: the caption ids of every rank, "
+                         "[N*B, new_tokens]) as DIR/sequences.npy (float64: token ids are exact), so that two builds can be "
+                         "compared output for output on identical seeded inputs")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.dump_outputs and a.eos_mix:
+        ap.error("--dump-outputs is wired for the timed step loop, not --eos-mix")
     if a.model is None:
         a.model = "gar_8b" if a.workload == "video" else "gar_1b"
     if a.workload == "video" and a.max_num_tiles == 16:
@@ -459,6 +471,27 @@ def self_launch(args, argv):
     return rc
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64 (int64 token ids below 2^53 are exact). An array
+    larger than its share of DUMP_LIMIT_BYTES is written as a fixed sample of its rows (seed 0, sorted) next to
+    <name>_rows.npy, the indices of those rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().to(torch.float64).numpy()
+        if a.nbytes > share:
+            row_bytes = max(1, a.nbytes // max(1, a.shape[0]))
+            keep = max(1, share // 2 // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def load_runtime(spec):
     import importlib
     mod, _, attr = spec.partition(":")
@@ -612,6 +645,8 @@ def main(argv=None, runtime=None):
     if rank == 0:       # every rank's [B, new_tokens] ids arrived on rank 0 in the last step
         assert caps is not None and len(caps) == world and all(tuple(c.shape) == (args.batch, args.new_tokens) for c in caps)
         gathered_shape = list(torch.cat([c.cpu() for c in caps]).shape)        # [world * B, new_tokens] on rank 0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"sequences": torch.cat([c.cpu() for c in caps])})
     timers, ops.KERNEL_TIMERS = ops.KERNEL_TIMERS, None
     bad_inputs = 0
     for f in input_flags:

@@ -126,6 +126,37 @@ def test_bench_control_flow_world8(tmp_path):
     assert len(seen) == 32
 
 
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` (CPU stub, one rank): DIR/sequences.npy holds, in float64, the caption ids the LAST timed step
+    returned; a second run with the same arguments writes the same array; --steps sets the number of timed steps."""
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["PYTHONPATH"] = os.pathsep.join([ROOT, os.path.join(ROOT, "tests"), env.get("PYTHONPATH", "")])
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--batch", "3", "--new-tokens", "4", "--model", "tiny", "--no-cpu-baseline", "--max-num-tiles", "4",
+                              "--runtime", "bench_stub:StubRuntime", "--dump-outputs", str(d_out)],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 3 * 3 / (d["ms_per_step"] * 3 / 1e3)) < 1e-6 * d["value"]
+        assert sorted(os.listdir(d_out)) == ["sequences.npy"]
+        dumps.append(np.load(d_out / "sequences.npy"))
+    a = dumps[0]
+    assert a.dtype == np.float64 and a.shape == (3, 4)
+    # step 1 + 3 - 1 = 3 is the last timed step: batch 3 % pool 2 = 1 holds regions 3, 4, 5; the stub's caption of region i
+    # is 3 i, 3 i + 1, ...
+    assert a.tolist() == [[3 * i + j for j in range(4)] for i in (3, 4, 5)]
+    assert np.array_equal(dumps[0], dumps[1])
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], env=env,
+                         capture_output=True, text=True, timeout=300)
+    assert bad.returncode != 0 and "--steps" in bad.stderr
+
+
 def test_dry_run_prints_the_launch_plan():
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry-run"], capture_output=True, text=True,
