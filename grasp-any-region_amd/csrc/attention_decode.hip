@@ -637,3 +637,488 @@ extern "C" int gar_attention_decode_qkv(int dtype, const void* qkv, const float*
     const decode_qkv_args fa = {(const bf16_t*)qkv, cos, sin, q_scale, qk_strip_order ? 1 : 0};
     return launch_decode(nullptr, hd, Kc, Vc, O, B, Hq, Hkv, hd, Smax, pos_dev, left_pad, max_splits, workspace, fa, stream);
 }
+
+// =====================================================================================================================
+// FP8 KV cache (GARModel(kv_cache_dtype="fp8"), ABI 16): OCP e4m3fn bytes Kc8 / Vc8 [B, Hkv, Smax, hd] and one f32 scale per
+// (sequence, kv head, position) in Ks / Vs [B, Hkv, Smax], K and V apart. A 16-bit vector x of hd values (K after RoPE) is
+//   amax = max|x|, inv = 448 / amax, q = e4m3(RNE(x * inv)), scale = amax / 448
+//   inv not finite (amax == 0, or amax < 448 / FLT_MAX ~ 1.3e-36 — bf16 reaches it, fp16 cannot): q = 0, scale = 0
+// in exactly these f32 operations: (x.float() * inv).to(torch.float8_e4m3fn) restates it byte for byte (|x * inv| <= 448
+// rounds inside the format, so the conversion never saturates; the inv = inf case above is excluded, 0 * inf would be NaN). The decode kernels dequantize by scaling, not per element:
+// score_j = (q . k8_j) * sk_j, and the softmax weight p_j enters the PV product as p_j * sv_j (the normaliser sums p_j).
+#define FP8_MAX 448.0f
+
+// four f32 (already times inv) -> four e4m3 bytes, byte i = element i (v_cvt_pk_fp8_f32: round to nearest even)
+__device__ __forceinline__ unsigned int pk4_fp8(float a, float b, float c, float d) {
+    const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    return (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+}
+// eight e4m3 bytes -> the MFMA operand of the 16-bit type (exact: e4m3 values are bf16 / fp16 values)
+__device__ __forceinline__ bf16x8 fp8x8_to_h16(u32x2 w) {
+#if GAR_HALF_F16
+    const h16x2_hw_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[0], 1.0f, false);
+    const h16x2_hw_t b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[0], 1.0f, true);
+    const h16x2_hw_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[1], 1.0f, false);
+    const h16x2_hw_t d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[1], 1.0f, true);
+#else
+    const bf16x2_hw_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[0], 1.0f, false);
+    const bf16x2_hw_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[0], 1.0f, true);
+    const bf16x2_hw_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[1], 1.0f, false);
+    const bf16x2_hw_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[1], 1.0f, true);
+#endif
+    const u32x4 r = {__builtin_bit_cast(unsigned int, a), __builtin_bit_cast(unsigned int, b), __builtin_bit_cast(unsigned int, c),
+                     __builtin_bit_cast(unsigned int, d)};
+    return __builtin_bit_cast(bf16x8, r);
+}
+
+// ---- gar_kv_quantize_fp8: one wave per (position, kv head, sequence); lanes 0..31 quantize the K vector, 32..63 the V vector
+template <int HD>
+__global__ __launch_bounds__(256) void kv_quantize_fp8_kernel(const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
+                                                              int src_stride, uint8_t* __restrict__ K8, uint8_t* __restrict__ V8,
+                                                              float* __restrict__ Ks, float* __restrict__ Vs, int Hkv, int Smax,
+                                                              int kv_start, int S) {
+    constexpr int E = HD / 32;                  // values per lane
+    const int lane = threadIdx.x & 63;
+    const int pos = kv_start + blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pos >= S) return;                       // (uniform per wave)
+    const int kvh = blockIdx.y, b = blockIdx.z;
+    const bool isv = lane >= 32;
+    const int l = lane & 31;
+    const int64_t sl = (int64_t)b * Hkv + kvh;
+    const bf16_t* src = (isv ? V : K) + (sl * src_stride + pos) * HD + l * E;
+    float x[E];
+    if constexpr (E == 2) {
+        const unsigned int w = *reinterpret_cast<const unsigned int*>(src);
+        x[0] = unpk_lo(w); x[1] = unpk_hi(w);
+    } else {
+        const u32x2 w = *reinterpret_cast<const u32x2*>(src);
+        x[0] = unpk_lo(w[0]); x[1] = unpk_hi(w[0]); x[2] = unpk_lo(w[1]); x[3] = unpk_hi(w[1]);
+    }
+    float a = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) a = fmaxf(a, fabsf(x[e]));
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));      // within the 32-lane half
+    const float inv = FP8_MAX / a;
+    const bool live = inv < INFINITY;           // amax > 0 and 448 / amax finite
+    uint8_t* dst = (isv ? V8 : K8) + (sl * Smax + pos) * HD + l * E;
+    if constexpr (E == 2) {
+        const unsigned int w = live ? (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv, x[1] * inv, 0, false) : 0u;
+        *reinterpret_cast<uint16_t*>(dst) = (uint16_t)(w & 0xffffu);
+    } else {
+        *reinterpret_cast<unsigned int*>(dst) = live ? pk4_fp8(x[0] * inv, x[1] * inv, x[2] * inv, x[3] * inv) : 0u;
+    }
+    if (l == 0) (isv ? Vs : Ks)[sl * Smax + pos] = live ? a / FP8_MAX : 0.f;
+}
+
+extern "C" int gar_kv_quantize_fp8(int dtype, const void* K, const void* V, int src_stride, void* Kc8, void* Vc8, float* Ks,
+                                   float* Vs, int B, int Hkv, int hd, int Smax, int kv_start, int S, gar_stream_t stream) {
+    GAR_CHECK_ARG(K && V && Kc8 && Vc8 && Ks && Vs, "kv_quantize_fp8: null pointer");
+    GAR_CHECK_ARG(dtype == GAR_BF16, "kv_quantize_fp8: 16-bit source only (the fp8 cache has no parity mode)");
+    GAR_CHECK_ARG(hd == 64 || hd == 128, "kv_quantize_fp8: head_dim %d not built (64, 128)", hd);
+    GAR_CHECK_ARG(B > 0 && Hkv > 0 && 0 <= kv_start && kv_start <= S && S <= Smax && S <= src_stride,
+                  "kv_quantize_fp8: need 0 <= kv_start <= S <= min(Smax, src_stride)");
+    if (kv_start == S) return GAR_OK;
+    GAR_CHECK_ARG(((uintptr_t)K & 7) == 0 && ((uintptr_t)V & 7) == 0 && ((uintptr_t)Kc8 & 3) == 0 && ((uintptr_t)Vc8 & 3) == 0,
+                  "kv_quantize_fp8: misaligned pointer");
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((S - kv_start + 3) / 4, Hkv, B);
+    if (hd == 64)
+        hipLaunchKernelGGL(kv_quantize_fp8_kernel<64>, grid, dim3(256), 0, s, (const bf16_t*)K, (const bf16_t*)V, src_stride,
+                           (uint8_t*)Kc8, (uint8_t*)Vc8, Ks, Vs, Hkv, Smax, kv_start, S);
+    else
+        hipLaunchKernelGGL(kv_quantize_fp8_kernel<128>, grid, dim3(256), 0, s, (const bf16_t*)K, (const bf16_t*)V, src_stride,
+                           (uint8_t*)Kc8, (uint8_t*)Vc8, Ks, Vs, Hkv, Smax, kv_start, S);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
+// ---- gar_attention_decode_fp8 / gar_attention_decode_qkv_fp8 ---------------------------------------------------------
+// The structure of decode_attn_lds_kernel at half the bytes: every wave DMAs its 64-kv tiles — K tile | V tile (64 rows of
+// HD bytes each) and the tile's 64 K | 64 V scales — into a private LDS region, now double-buffered (two tiles in flight per
+// wave: HD 64 keeps 2 blocks per CU, HD 128 one, ~130 KiB of loads in flight per CU either way). The scales have three
+// buffers, so that a tile's scales are read where they are used, after the K / V buffer has been re-armed (registers). Row r of a tile keeps its 16-byte
+// chunk c at position c ^ key(r), key = (r >> 2) & 3 (HD 64) / (r >> 1) & 7 (HD 128): the 32 rows of a fragment read spread
+// over 16 chunk positions. K fragments are one ds_read_b64 (8 bytes of a row); V fragments (8 kv of one d column) are eight
+// byte reads. Both stay raw bytes in registers until the region is re-armed, then become 16-bit operands in registers.
+template <int HD>
+__device__ __forceinline__ int fp8_key(int r) { return HD == 64 ? (r >> 2) & 3 : (r >> 1) & 7; }
+template <int HD>
+__device__ __forceinline__ int fp8_off(int r, int d) { return r * HD + ((((d >> 4) ^ fp8_key<HD>(r)) << 4) | (d & 15)); }
+
+// the step's new key (rotated, rounded to the 16-bit type) and value of (b, kvh): quantized as gar_kv_quantize_fp8 does,
+// appended at cache row `pos` with their scales, and patched into the wave's LDS tile (row pos & 63). Every lane calls it.
+template <int HD>
+__device__ __forceinline__ void append_new_kv_fp8(const decode_qkv_args& fa, uint8_t* Kp, uint8_t* Vp, float* Ksp, float* Vsp,
+                                                  char* buf, char* sbuf, int b, int Hq, int Hkv, int kvh, int lane, int pos,
+                                                  int rp) {
+    constexpr int HALF = HD / 2, TB = 64 * HD;
+    const int r = pos & 63;
+    const bf16_t* row = fa.raw + (int64_t)b * (Hq + 2 * Hkv) * HD;
+    const bool kl = lane < HALF / 8, vl = lane < HD / 8;
+    const int i8 = (lane & (HD / 8 - 1)) * 8;
+    float x1[8], x2[8], v[8];
+    float ka = 0.f, va = 0.f;
+    if (kl) {
+        const bf16_t* rk = row + (Hq + kvh) * HD;
+        float c[8], sv[8];
+        ld8(rk + strip_col_d<HD>(i8, fa.strip), x1);
+        ld8(rk + strip_col_d<HD>(HALF + i8, fa.strip), x2);
+        ld8(fa.cs + (int64_t)rp * HALF + i8, c);
+        ld8(fa.sn + (int64_t)rp * HALF + i8, sv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            rope_half_pair(x1[e], x2[e], c[e], sv[e], 1.0f, x1[e], x2[e]);
+            x1[e] = unpk_lo(pack_bf2(x1[e], 0.f));             // the 16-bit key gar_attention_decode_qkv would append
+            x2[e] = unpk_lo(pack_bf2(x2[e], 0.f));
+            ka = fmaxf(ka, fmaxf(fabsf(x1[e]), fabsf(x2[e])));
+        }
+    }
+    if (vl) {
+        ld8(row + (Hq + Hkv + kvh) * HD + i8, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) va = fmaxf(va, fabsf(v[e]));
+    }
+#pragma unroll
+    for (int o = 1; o < HD / 8; o <<= 1) {
+        ka = fmaxf(ka, __shfl_xor(ka, o, 64));
+        va = fmaxf(va, __shfl_xor(va, o, 64));
+    }
+    const float kinv = FP8_MAX / ka, vinv = FP8_MAX / va;
+    const bool klive = kinv < INFINITY, vlive = vinv < INFINITY;        // as gar_kv_quantize_fp8
+    if (kl) {
+        u32x2 w1 = {pk4_fp8(x1[0] * kinv, x1[1] * kinv, x1[2] * kinv, x1[3] * kinv),
+                    pk4_fp8(x1[4] * kinv, x1[5] * kinv, x1[6] * kinv, x1[7] * kinv)};
+        u32x2 w2 = {pk4_fp8(x2[0] * kinv, x2[1] * kinv, x2[2] * kinv, x2[3] * kinv),
+                    pk4_fp8(x2[4] * kinv, x2[5] * kinv, x2[6] * kinv, x2[7] * kinv)};
+        const u32x2 z = {0u, 0u};
+        if (!klive) { w1 = z; w2 = z; }
+        *reinterpret_cast<u32x2*>(Kp + (int64_t)pos * HD + i8) = w1;
+        *reinterpret_cast<u32x2*>(Kp + (int64_t)pos * HD + HALF + i8) = w2;
+        *reinterpret_cast<u32x2*>(buf + fp8_off<HD>(r, i8)) = w1;
+        *reinterpret_cast<u32x2*>(buf + fp8_off<HD>(r, HALF + i8)) = w2;
+    }
+    if (vl) {
+        u32x2 w = {pk4_fp8(v[0] * vinv, v[1] * vinv, v[2] * vinv, v[3] * vinv),
+                   pk4_fp8(v[4] * vinv, v[5] * vinv, v[6] * vinv, v[7] * vinv)};
+        if (!vlive) w = u32x2{0u, 0u};
+        *reinterpret_cast<u32x2*>(Vp + (int64_t)pos * HD + i8) = w;
+        *reinterpret_cast<u32x2*>(buf + TB + fp8_off<HD>(r, i8)) = w;
+    }
+    if (lane == 0) {
+        const float sk = klive ? ka / FP8_MAX : 0.f, sv = vlive ? va / FP8_MAX : 0.f;
+        Ksp[pos] = sk;
+        Vsp[pos] = sv;
+        reinterpret_cast<float*>(sbuf)[r] = sk;
+        reinterpret_cast<float*>(sbuf + 256)[r] = sv;
+    }
+    asm volatile("" ::: "memory");          // the fragment reads that follow stay behind the patch
+}
+
+template <int HD>
+__global__ __launch_bounds__(256, HD == 64 ? 2 : 1) void decode_attn_fp8_kernel(const bf16_t* __restrict__ Q, uint8_t* K8, uint8_t* V8,
+                                                                               float* Ks, float* Vs, float* __restrict__ part,
+                                                                               int Hq, int Hkv, int kv_stride,
+                                                                               const int32_t* __restrict__ kv_len_dev,
+                                                                               const int32_t* __restrict__ kv_start,
+                                                                               bf16_t* __restrict__ O_direct, const decode_qkv_args fa,
+                                                                               int64_t q_stride) {
+    constexpr int NKD = HD / 16, NDB = HD / 32;
+    constexpr int TB = 64 * HD;                 // bytes of a K (or V) tile
+    constexpr int WAVE_LDS = 2 * 2 * TB + 3 * 512;  // [2 stages][K tile | V tile], [3][64 K scales | 64 V scales]
+    constexpr int NP = TB / 1024;               // 1-KiB DMA pieces per tile
+    constexpr int NPS = 2 * NP + 2;             // DMA instructions per stage
+    constexpr int CPR = HD / 16;                // 16-byte chunks per row
+    extern __shared__ __attribute__((aligned(16))) char smem[];     // [4 waves][WAVE_LDS] then red
+    float (*red)[8][HD + 2] = reinterpret_cast<float (*)[8][HD + 2]>(smem + 4 * WAVE_LDS);
+    const int kv_len = kv_len_dev[0] + (fa.raw ? 1 : 0);            // fused: kv_len_dev is the step's position, the new row included
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, h = lane >> 5;
+    const int split = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int G = Hq / Hkv;
+    const int ntiles = (kv_len + 63) / 64;
+    const int kv_lo = kv_start ? max(min(kv_start[b], kv_len - 1), 0) : 0;
+    const int t_lo = kv_lo >> 6;
+    const int per = (ntiles - t_lo + nsplit - 1) / nsplit;
+    const int t0 = t_lo + split * per, t1 = min(ntiles, t0 + per);
+    const int64_t sl = (int64_t)b * Hkv + kvh;
+    uint8_t* Kp = K8 + sl * (int64_t)kv_stride * HD;
+    uint8_t* Vp = V8 + sl * (int64_t)kv_stride * HD;
+    float* Ksp = Ks + sl * (int64_t)kv_stride;
+    float* Vsp = Vs + sl * (int64_t)kv_stride;
+    const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, kv_stride * HD, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, kv_stride * HD, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsKs = __builtin_amdgcn_make_buffer_rsrc((void*)Ksp, 0, kv_stride * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsVs = __builtin_amdgcn_make_buffer_rsrc((void*)Vsp, 0, kv_stride * 4, 0x00020000);
+    char* region = smem + wave * WAVE_LDS;
+    char* sregion = region + 4 * TB;
+    // DMA piece i: rows i * (64 / CPR) + lane / CPR, LDS chunk position lane % CPR <- global chunk position ^ key(row); the
+    // key of such a row depends on i only through its parity (HD 128) or not at all (HD 64)
+    int offs[2];
+#pragma unroll
+    for (int par = 0; par < 2; ++par) {
+        const int r = par * (64 / CPR) + lane / CPR;
+        offs[par] = r * HD + (((lane % CPR) ^ fp8_key<HD>(r)) << 4);
+    }
+    auto stage = [&](int t, char* dst, char* sdst) {
+        const int tb = t * TB;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, LDS_AS(dst + i * 1024), 16, offs[i & 1] + (tb + (i & ~1) * 1024), 0, 0,
+                                                     DA_KV_AUX);
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, LDS_AS(dst + TB + i * 1024), 16, offs[i & 1] + (tb + (i & ~1) * 1024), 0, 0,
+                                                     DA_KV_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsKs, LDS_AS(sdst), 4, (t * 64 + lane) * 4, 0, 0, DA_KV_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsVs, LDS_AS(sdst + 256), 4, (t * 64 + lane) * 4, 0, 0, DA_KV_AUX);
+    };
+    bf16x8 qf[NKD];
+    const int rp = max(kv_len - 1 - (kv_start ? kv_start[b] : 0), 0);         // fused: RoPE position of the step's token
+    if (fa.raw) {
+        load_q_rotated<HD>(qf, fa, b, Hq, Hkv, kvh * G + min(l31, G - 1), l31 < G, h, rp);
+    } else {
+        const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        const bf16_t* qp = Q + ((int64_t)b * Hq + kvh * G + min(l31, G - 1)) * q_stride;
+#pragma unroll
+        for (int kd = 0; kd < NKD; ++kd)
+            qf[kd] = l31 < G ? *reinterpret_cast<const bf16x8*>(qp + kd * 16 + h * 8) : z;
+    }
+    f32x16 o[NDB];
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+    const int prow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // fragment addresses as lane base + compile-time offset (the swizzle key of a row is a lane part XOR a constant):
+    //   K: row blk*32 + prow (key(row + 32) = key(row)), bytes kd*16 + 8h .. +7
+    //   V: rows c4*16 + 8h + e, column d*32 + l31: chunk (2d + l31/16) ^ key, key = 2h + e/4 (HD 64) / 4h + e/2 (HD 128)
+    int kaddr[NKD], vaddr[2 * NDB];
+#pragma unroll
+    for (int kd = 0; kd < NKD; ++kd) kaddr[kd] = fp8_off<HD>(prow, kd * 16 + h * 8);
+    {
+        const int lanepart = (l31 >> 4) ^ (HD == 64 ? 2 * h : 4 * h);
+#pragma unroll
+        for (int c = 0; c < 2 * NDB; ++c) vaddr[c] = TB + 8 * h * HD + ((lanepart ^ c) << 4) + (l31 & 15);
+    }
+
+    int t = t0 + wave;
+    if (t < t1) stage(t, region, sregion);
+    if (t + 4 < t1) stage(t + 4, region + 2 * TB, sregion + 512);
+    for (int it = 0, s3 = 0; t < t1; t += 4, ++it, s3 = s3 == 2 ? 0 : s3 + 1) {
+        char* buf = region + (it & 1) * 2 * TB;
+        char* sbuf = sregion + s3 * 512;
+        if (t + 4 < t1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPS) : "memory");      // tile t in; tile t + 4 may be out
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (fa.raw && t == ntiles - 1)           // the tile that holds the step's own row (nothing behind it in flight)
+            append_new_kv_fp8<HD>(fa, Kp, Vp, Ksp, Vsp, buf, sbuf, b, Hq, Hkv, kvh, lane, kv_len - 1, rp);
+        u32x2 kr[2][NKD], vr[NDB][4];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int kd = 0; kd < NKD; ++kd)
+                kr[blk][kd] = *reinterpret_cast<const u32x2*>(buf + kaddr[kd] + blk * 32 * HD);
+#pragma unroll
+        for (int d = 0; d < NDB; ++d)
+#pragma unroll
+            for (int c4 = 0; c4 < 4; ++c4) {
+                unsigned int by[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    by[e] = *reinterpret_cast<const uint8_t*>(buf + vaddr[(2 * d) ^ (HD == 64 ? e >> 2 : e >> 1)] + (c4 * 16 + e) * HD);
+                vr[d][c4] = u32x2{by[0] | (by[1] << 8) | (by[2] << 16) | (by[3] << 24),
+                                  by[4] | (by[5] << 8) | (by[6] << 16) | (by[7] << 24)};
+                __builtin_amdgcn_sched_barrier(0);  // pack as the bytes arrive: 8 VGPRs of bytes live, not 8 x HD / 8
+            }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (t + 8 < t1) stage(t + 8, buf, sregion + (s3 == 0 ? 2 : s3 - 1) * 512);   // re-arm: tile t's bytes are in registers now
+        __builtin_amdgcn_sched_barrier(0);
+        // [blk][g][half]: scales of kv blk*32 + g*16 + 8h + 4 half + 0..3 (K scales at sbuf, V scales at sbuf + 256)
+        auto ld_scales = [&](f32x4 (&sc)[2][2][2], const char* p) {
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf)
+                        sc[blk][g][hf] = *reinterpret_cast<const f32x4*>(p + (blk * 32 + g * 16 + h * 8 + hf * 4) * 4);
+        };
+        f32x4 sk[2][2][2];
+        ld_scales(sk, sbuf);
+        const int kv0 = t * 64;
+        f32x16 s[2];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int kd = 0; kd < NKD; ++kd)
+                s[blk] = MFMA_32x32x16(fp8x8_to_h16(kr[blk][kd]), qf[kd], kd == 0 ? zero16 : s[blk]);
+        // s[blk][r] is kv kv0 + blk*32 + 16 (r >> 3) + 8h + (r & 7): scale, then mask (a masked row's scale may be anything)
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[blk][r] *= sk[blk][r >> 3][(r >> 2) & 1][r & 3];
+        __builtin_amdgcn_sched_barrier(0);      // the V scales load behind the K scales' last use (VGPRs)
+        f32x4 svs[2][2][2];
+        ld_scales(svs, sbuf + 256);
+        if (kv0 + 64 > kv_len || kv0 < kv_lo) {
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kv = kv0 + blk * 32 + ((r >> 3) << 4) + h * 8 + (r & 7);
+                    s[blk][r] = (kv < kv_len && kv >= kv_lo) ? s[blk][r] : -INFINITY;
+                }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[blk][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
+        m_run = m_new;
+        float ps = 0.f;
+        bf16x8 pf[2][2];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            float p[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float pr = __builtin_amdgcn_exp2f(s[blk][r] - m_use);
+                ps += pr;
+                p[r] = pr * svs[blk][r >> 3][(r >> 2) & 1][r & 3];
+            }
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                u32x4 w;
+                w[0] = cvt_pk_d(p[tt * 8 + 0], p[tt * 8 + 1]);
+                w[1] = cvt_pk_d(p[tt * 8 + 2], p[tt * 8 + 3]);
+                w[2] = cvt_pk_d(p[tt * 8 + 4], p[tt * 8 + 5]);
+                w[3] = cvt_pk_d(p[tt * 8 + 6], p[tt * 8 + 7]);
+                pf[blk][tt] = __builtin_bit_cast(bf16x8, w);
+            }
+        }
+        l_run = l_run * alpha + ps;
+#pragma unroll
+        for (int d = 0; d < NDB; ++d) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt)
+                    o[d] = MFMA_32x32x16(fp8x8_to_h16(vr[d][blk * 2 + tt]), pf[blk][tt], o[d]);
+        }
+    }
+    // ---- merge the four waves (LDS), one partial per block — as in decode_attn_lds_kernel
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (l31 < G) {
+        float* pp = &red[wave][l31][0];
+#pragma unroll
+        for (int d = 0; d < NDB; ++d)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pp[d * 32 + g4 * 8 + h * 4 + e] = o[d][g4 * 4 + e];
+        if (h == 0) { pp[HD] = m_run; pp[HD + 1] = l_tot; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < G * HD; idx += 256) {
+        const int g = idx / HD, d = idx % HD;
+        float m = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) m = fmaxf(m, red[w][g][HD]);
+        const float m_use = m == -INFINITY ? 0.f : m;
+        float acc = 0.f, l = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float sc = __builtin_amdgcn_exp2f(red[w][g][HD] - m_use);
+            acc += sc * red[w][g][d];
+            l += sc * red[w][g][HD + 1];
+        }
+        if (O_direct) {
+            const float inv = l > 0.f ? 1.0f / l : 0.f;
+            O_direct[((int64_t)b * Hq + kvh * G + g) * HD + d] = f2bf(acc * inv);
+            continue;
+        }
+        float* pp = part + ((((int64_t)b * Hkv + kvh) * nsplit + split) * G + g) * (HD + 2);
+        pp[d] = acc;
+        if (d == 0) { pp[HD] = m; pp[HD + 1] = l; }
+    }
+}
+
+template <int HD>
+static void launch_decode_fp8_hd(const void* q, int64_t q_stride, void* K8, void* V8, float* Ks, float* Vs, void* O, int B, int Hq,
+                                 int Hkv, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits,
+                                 void* workspace, const decode_qkv_args& fa, hipStream_t s) {
+    constexpr int lds = 4 * (4 * 64 * HD + 3 * 512) + 4 * 8 * (HD + 2) * 4;
+    static gar_once_per_device attr_once;
+    attr_once.run([&] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_fp8_kernel<HD>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    });
+    bf16_t* direct = max_splits == 1 ? (bf16_t*)O : nullptr;
+    hipLaunchKernelGGL(decode_attn_fp8_kernel<HD>, dim3(max_splits, Hkv, B), dim3(256), lds, s, (const bf16_t*)q, (uint8_t*)K8,
+                       (uint8_t*)V8, Ks, Vs, (float*)workspace, Hq, Hkv, Smax, kv_len_dev, kv_start, direct, fa, q_stride);
+    if (!direct)
+        hipLaunchKernelGGL((decode_combine_kernel<HD>), dim3(Hq, B), dim3(64), 0, s, (const float*)workspace, (bf16_t*)O, Hq, Hkv,
+                           max_splits);
+}
+
+static int launch_decode_fp8(const void* q, int64_t q_stride, void* K8, void* V8, float* Ks, float* Vs, void* O, int B, int Hq,
+                             int Hkv, int hd, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits,
+                             void* workspace, const decode_qkv_args& fa, gar_stream_t stream) {
+    GAR_CHECK_ARG(workspace && max_splits > 0 && max_splits <= 64, "attention_decode_fp8: workspace / max_splits (1..64)");
+    GAR_CHECK_ARG(((uintptr_t)K8 & 15) == 0 && ((uintptr_t)V8 & 15) == 0 && ((uintptr_t)Ks & 15) == 0 && ((uintptr_t)Vs & 15) == 0,
+                  "attention_decode_fp8: caches and scale planes must be 16-byte aligned");
+    if ((int64_t)Smax * hd >= ((int64_t)1 << 31)) {
+        gar_set_error("attention_decode_fp8: Smax %d x head_dim %d exceeds the 2 GiB per-slab range of the DMA-staged kernel", Smax, hd);
+        return GAR_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (hd == 64)
+        launch_decode_fp8_hd<64>(q, q_stride, K8, V8, Ks, Vs, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, s);
+    else
+        launch_decode_fp8_hd<128>(q, q_stride, K8, V8, Ks, Vs, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, s);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
+extern "C" int64_t gar_attention_decode_fp8_workspace(int B, int Hq, int hd, int max_splits) {
+    return gar_attention_decode_workspace(B, Hq, hd, max_splits);
+}
+
+extern "C" int gar_attention_decode_fp8(int dtype, const void* q, int64_t q_stride, const void* Kc8, const void* Vc8, const float* Ks,
+                                        const float* Vs, void* O, int B, int Hq, int Hkv, int hd, int Smax, const int32_t* kv_len_dev,
+                                        const int32_t* kv_start, int max_splits, void* workspace, gar_stream_t stream) {
+    GAR_CHECK_ARG(q && Kc8 && Vc8 && Ks && Vs && O && kv_len_dev, "attention_decode_fp8: null pointer");
+    GAR_CHECK_ARG(dtype == GAR_BF16, "attention_decode_fp8: 16-bit query only (the fp8 cache has no parity mode)");
+    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "attention_decode_fp8: Hq/Hkv must be <= 8");
+    GAR_CHECK_ARG(Smax % 64 == 0, "attention_decode_fp8: Smax must be a multiple of 64");
+    GAR_CHECK_ARG(hd == 64 || hd == 128, "attention_decode_fp8: head_dim %d not built (64, 128)", hd);
+    if (q_stride <= 0) q_stride = hd;
+    GAR_CHECK_ARG(q_stride % hd == 0 && ((uintptr_t)q & 15) == 0, "attention_decode_fp8: q_stride must be a multiple of head_dim, q 16-byte aligned");
+    const decode_qkv_args none = {nullptr, nullptr, nullptr, 0.f, 0};
+    return launch_decode_fp8(q, q_stride, const_cast<void*>(Kc8), const_cast<void*>(Vc8), const_cast<float*>(Ks), const_cast<float*>(Vs),
+                             O, B, Hq, Hkv, hd, Smax, kv_len_dev, kv_start, max_splits, workspace, none, stream);
+}
+
+extern "C" int gar_attention_decode_qkv_fp8(int dtype, const void* qkv, const float* cos, const float* sin, void* Kc8, void* Vc8,
+                                            float* Ks, float* Vs, void* O, int B, int Hq, int Hkv, int hd, int Smax,
+                                            const int32_t* pos_dev, const int32_t* left_pad, float q_scale, int qk_strip_order,
+                                            int max_splits, void* workspace, gar_stream_t stream) {
+    GAR_CHECK_ARG(qkv && cos && sin && Kc8 && Vc8 && Ks && Vs && O && pos_dev, "attention_decode_qkv_fp8: null pointer");
+    GAR_CHECK_ARG(dtype == GAR_BF16, "attention_decode_qkv_fp8: 16-bit qkv only (the fp8 cache has no parity mode)");
+    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "attention_decode_qkv_fp8: Hq/Hkv must be <= 8");
+    GAR_CHECK_ARG(Smax % 64 == 0, "attention_decode_qkv_fp8: Smax must be a multiple of 64");
+    GAR_CHECK_ARG(hd == 64 || hd == 128, "attention_decode_qkv_fp8: head_dim %d not built (64, 128)", hd);
+    GAR_CHECK_ARG(((uintptr_t)qkv & 15) == 0, "attention_decode_qkv_fp8: qkv must be 16-byte aligned");
+    const decode_qkv_args fa = {(const bf16_t*)qkv, cos, sin, q_scale, qk_strip_order ? 1 : 0};
+    return launch_decode_fp8(nullptr, hd, Kc8, Vc8, Ks, Vs, O, B, Hq, Hkv, hd, Smax, pos_dev, left_pad, max_splits, workspace, fa, stream);
+}

@@ -293,11 +293,13 @@ class ContinuousBatcher:
         P, T = self.P, self.T
         rows_t = torch.tensor(rows, dtype=torch.int64, device=dev)
         offs = [P - n for n in lens]
-        # keys / values of sequence i: staging rows S - n .. S - 1 -> decode row rows[i], cache rows P - n .. P - 1
+        # keys / values of sequence i: staging rows S - n .. S - 1 -> decode row rows[i], cache rows P - n .. P - 1 (an fp8
+        # cache moves its scale planes Ks / Vs with the bytes)
+        planes = [k for k in ("Kc", "Vc", "Ks", "Vs") if k in st]
         for i, r in enumerate(rows):
             n = lens[i]
-            st["Kc"][:, r, :, P - n:P].copy_(sg["Kc"][:, i, :, S - n:S])
-            st["Vc"][:, r, :, P - n:P].copy_(sg["Vc"][:, i, :, S - n:S])
+            for k in planes:
+                st[k][:, r, :, P - n:P].copy_(sg[k][:, i, :, S - n:S])
         first = sg["cur"][:G]
         st["cur"].index_copy_(0, rows_t, first)
         st["left_pad"].index_copy_(0, rows_t, torch.tensor(offs, dtype=torch.int32, device=dev))
@@ -323,13 +325,13 @@ class ContinuousBatcher:
             return False
         st, P, T = self.st, self.P, self.T
         dT = min(row.start_col for _, row in live)          # >= 0; columns in front of it belong to retired rows
+        planes = [k for k in ("Kc", "Vc", "Ks", "Vs") if k in st]      # (Ks / Vs: the scale planes of an fp8 cache)
         for r, row in live:
             lo = row.left_pad
-            k = st["Kc"][:, r, :, lo:P].clone()
-            st["Kc"][:, r, :, lo - d:P - d].copy_(k)
-            v = st["Vc"][:, r, :, lo:P].clone()
-            st["Vc"][:, r, :, lo - d:P - d].copy_(v)
-            del k, v
+            for name in planes:
+                x = st[name][:, r, :, lo:P].clone()
+                st[name][:, r, :, lo - d:P - d].copy_(x)
+                del x
             row.left_pad -= d
         if dT > 0:
             keep = self.out_tokens[:, dT:T].clone()

@@ -357,8 +357,19 @@ class GARModel:
     PRUNE_LAST_PREFILL_LAYER = True
 
     def __init__(self, config: GARConfig, weights: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16,
-                 device: str = "cuda:0", prefill_chunk: Optional[int] = None, keep_plain_weights: bool = False):
+                 device: str = "cuda:0", prefill_chunk: Optional[int] = None, keep_plain_weights: bool = False,
+                 kv_cache_dtype: Optional[str] = None):
         self.device = torch.device(device)
+        # the decode KV cache: None / "auto" = the model dtype; "fp8" = OCP e4m3fn bytes + one f32 scale per (layer, row, kv head,
+        # position), K and V apart (include/gar_hip.h, FP8 KV cache). A property of the model, like its dtype: one model = one
+        # configuration. The prompt's own attention stays 16-bit, so prefill logits and the first token do not change.
+        if kv_cache_dtype not in (None, "auto", "fp8"):
+            raise hip.GarError(f"kv_cache_dtype {kv_cache_dtype!r}: None, 'auto' or 'fp8'")
+        self.kv_fp8 = kv_cache_dtype == "fp8"
+        if self.kv_fp8 and dtype not in HALF_DTYPES:
+            raise hip.GarError(f"kv_cache_dtype='fp8' needs a 16-bit model (bfloat16 / float16), not {dtype}: "
+                               "float32 is the parity mode")
+        self.kv_cache_dtype = "fp8" if self.kv_fp8 else None
         # bf16 keeps ONE copy of every weight: the norm-folded forms (ViT qkv / fc1, Llama qkv / gate-up) serve the tile GEMMs
         # (row_scale), the decode GEMVs (norm_folded) and — behind a unit-gain norm pass — the shapes neither takes.
         # keep_plain_weights=True also keeps the un-folded copies (+1.6 GB GAR-1B, +11 GB GAR-8B): A/B switch for FOLD_NORMS = False
@@ -390,11 +401,12 @@ class GARModel:
         return cls(config, synthetic_weights(config, seed), dtype, device, **kw)
 
     @classmethod
-    def from_pretrained(cls, path: str, dtype=torch.bfloat16, device="cuda:0", config: GARConfig = None):
+    def from_pretrained(cls, path: str, dtype=torch.bfloat16, device="cuda:0", config: GARConfig = None,
+                        kv_cache_dtype: Optional[str] = None):
         import os
         if config is None:
             config = GARConfig.from_json_file(os.path.join(path, "config.json"))
-        return cls(config, normalize_checkpoint(config, load_weights(path)), dtype, device)
+        return cls(config, normalize_checkpoint(config, load_weights(path)), dtype, device, kv_cache_dtype=kv_cache_dtype)
 
     @classmethod
     def from_shapes(cls, config: GARConfig, dtype=torch.bfloat16, device="cuda:0"):
@@ -929,9 +941,10 @@ class GARModel:
                 for wk in [w for w in self._ws if w[0] in ("decode", "head") and w[1] == old[1]]:
                     self._ws.pop(wk, None)
         L, Hkv, hd = t.num_hidden_layers, t.num_key_value_heads, t.head_dim
+        kv_dt = torch.uint8 if self.kv_fp8 else None
         st = dict(
-            Kc=self._buf(key, "Kc", (L, B, Hkv, Smax, hd), zero=True),
-            Vc=self._buf(key, "Vc", (L, B, Hkv, Smax, hd), zero=True),      # row-major like K: an append is one row
+            Kc=self._buf(key, "Kc", (L, B, Hkv, Smax, hd), kv_dt, zero=True),
+            Vc=self._buf(key, "Vc", (L, B, Hkv, Smax, hd), kv_dt, zero=True),      # row-major like K: an append is one row
             counters=self._buf(key, "counters", (4,), torch.int32, zero=True),   # [pos, kv_len, step, -]
             cur=self._buf(key, "cur", (B,), torch.int64, zero=True),
             # first real row of every sequence (left-padded batch; zeros otherwise): read by the qkv-post and attention
@@ -948,6 +961,9 @@ class GARModel:
             sampling=False,
             slot=slot,
         )
+        if self.kv_fp8:     # e4m3 bytes in Kc / Vc, their scales here
+            st["Ks"] = self._buf(key, "Ks", (L, B, Hkv, Smax), torch.float32, zero=True)
+            st["Vs"] = self._buf(key, "Vs", (L, B, Hkv, Smax), torch.float32, zero=True)
         return key, st
 
     def _prefill(self, embeds: torch.Tensor, st, Smax: int, b0: int = 0):
@@ -990,12 +1006,18 @@ class GARModel:
         if L > 1 or not prune:
             att = self._buf(key, "att", (M, Hq * hd))
             ff = self._buf(key, "ff", (M, F))
+        # fp8 cache: the prompt kernels write a 16-bit K / V scratch of the layer (kv stride Spad) and read it for the prompt's
+        # own attention; one quantize launch per layer then fills the fp8 cache the decode steps read
+        kv_stride = Spad if self.kv_fp8 else Smax
         for li, ly in enumerate(self.layers):
             last = li + 1 == L
-            Kc, Vc = st["Kc"][li][b0:b0 + B], st["Vc"][li][b0:b0 + B]         # this chunk's rows of the shared cache
+            if self.kv_fp8:
+                Kc, Vc = self._buf(key, "K16", (B, Hkv, Spad, hd)), self._buf(key, "V16", (B, Hkv, Spad, hd))
+            else:
+                Kc, Vc = st["Kc"][li][b0:b0 + B], st["Vc"][li][b0:b0 + B]         # this chunk's rows of the shared cache
             # ---- q / k / v of EVERY row (the decode steps read this layer's K / V rows too)
             if fused_qkv:
-                if not ops.gemm_qkv_rope_llm(h, ly["qkv_f"], Q, Kc, Vc, cos, sin, B, S, Spad, Hq, Hkv, hd, Smax, 0, None,
+                if not ops.gemm_qkv_rope_llm(h, ly["qkv_f"], Q, Kc, Vc, cos, sin, B, S, Spad, Hq, Hkv, hd, kv_stride, 0, None,
                                              q_scale, left_pad=lp, row_scale=rstd):
                     raise hip.GarError("fused qkv GEMM refused a shape gar_gemm_tile_takes() accepted")
             else:
@@ -1008,11 +1030,14 @@ class GARModel:
                 else:
                     ops.rmsnorm(h, ly["ln1"], t.rms_norm_eps, out=xn)
                     ops.gemm(xn, ly["qkv"], qb)
-                ops.llm_qkv_post(qb, cos, sin, Q, Kc, Vc, B, S, Spad, Hq, Hkv, hd, Smax, 0, None, q_scale, left_pad=lp,
+                ops.llm_qkv_post(qb, cos, sin, Q, Kc, Vc, B, S, Spad, Hq, Hkv, hd, kv_stride, 0, None, q_scale, left_pad=lp,
                                  strip_order=strip)
+            if self.kv_fp8:
+                ops.kv_quantize_fp8(Kc, Vc, st["Kc"][li][b0:b0 + B], st["Vc"][li][b0:b0 + B], st["Ks"][li][b0:b0 + B],
+                                    st["Vs"][li][b0:b0 + B], B, Hkv, hd, Smax, S)
             if last and prune:
-                return self._prefill_tail(ly, h, Q, Kc, Vc, st, key, B, S, Spad, Smax, lp)
-            ops.attention(Q, Kc, Vc, att, B, Hq, Hkv, hd, S, Spad, S, Smax, causal=True, kv_start=lp, v_row_major=True)
+                return self._prefill_tail(ly, h, Q, Kc, Vc, st, key, B, S, Spad, kv_stride, lp)
+            ops.attention(Q, Kc, Vc, att, B, Hq, Hkv, hd, S, Spad, S, kv_stride, causal=True, kv_start=lp, v_row_major=True)
             if fold:
                 ops.gemm(att, ly["o"], h, hip.EPI_RES, residual=h, row_stats=stats)
                 ops.row_stats_finalize(stats, C_l, t.rms_norm_eps, True, rstd)
@@ -1031,7 +1056,7 @@ class GARModel:
                 ops.gemm(ff, ly["down"], h, hip.EPI_RES, residual=h)
         return h.view(B, S, C_l)[:, S - 1, :]                                   # row-strided view [B, C]
 
-    def _prefill_tail(self, ly, h, Q, Kc, Vc, st, key, B, S, Spad, Smax, lp):
+    def _prefill_tail(self, ly, h, Q, Kc, Vc, st, key, B, S, Spad, kv_stride, lp):
         """The last layer of a prefill behind its qkv GEMM, for the LAST prompt row of each of the B sequences only
         (PRUNE_LAST_PREFILL_LAYER): single-row attention over the sequence's S cache rows with the split-KV decode kernel —
         the query is read in place from row S - 1 of Q [B, Hq, Spad, hd] — then o / RMSNorm / gate-up / down as B-row GEMMs on
@@ -1046,7 +1071,7 @@ class GARModel:
         kv_len.fill_(S)
         nsplit = max(1, min(self.DECODE_ATTN_MAX_SPLITS, self.DECODE_ATTN_BLOCKS // max(1, B * Hkv)))
         dws = self._buf(key, "attn_ws_last", (ops.attention_decode_workspace(B, Hq, hd, nsplit),), torch.uint8)
-        ops.attention_decode(Q[:, :, S - 1], Kc, Vc, attl, B, Hq, Hkv, hd, Smax, kv_len, nsplit, dws, kv_start=lp,
+        ops.attention_decode(Q[:, :, S - 1], Kc, Vc, attl, B, Hq, Hkv, hd, kv_stride, kv_len, nsplit, dws, kv_start=lp,
                              q_stride=Spad * hd)
         ops.gemm(attl, ly["o"], hl, hip.EPI_RES, residual=hl)
         if "gu_f" in ly and (self.FOLD_NORMS or "gu" not in ly):
@@ -1160,7 +1185,10 @@ class GARModel:
                     ops.rmsnorm(h, self.unit_rms if use_folded_w else ly["ln1"], t.rms_norm_eps, out=xn)
                 ops.gemm(xn, ly["qkv_f"] if use_folded_w else ly["qkv"], qkv)
             # bf16: RoPE, q scale and the cache append run inside the attention launch (one launch instead of two)
-            if not (self.DECODE_ATTN_TAKES_QKV and
+            if self.kv_fp8:     # the fp8 cache has only the fused form: the new row is quantized inside the launch
+                ops.attention_decode_qkv_fp8(qkv, cos, sin, st["Kc"][li], st["Vc"][li], st["Ks"][li], st["Vs"][li], att, B, Hq, Hkv,
+                                             hd, Smax, pos_dev, q_scale, nsplit, dws, left_pad=st["left_pad"], strip_order=strip)
+            elif not (self.DECODE_ATTN_TAKES_QKV and
                     ops.attention_decode_qkv(qkv, cos, sin, st["Kc"][li], st["Vc"][li], att, B, Hq, Hkv, hd, Smax, pos_dev,
                                              q_scale, nsplit, dws, left_pad=st["left_pad"], strip_order=strip)):
                 ops.llm_qkv_post(qkv, cos, sin, Q, st["Kc"][li], st["Vc"][li], B, 1, 1, Hq, Hkv, hd, Smax, 0, pos_dev, q_scale,
@@ -1482,7 +1510,7 @@ class GARModel:
     def _decode_graph(self, st, B, Smax, out_tokens, skey):
         """(graph, logits buffer of the captured step). out_tokens is a [:, :n] slice of the state's [B, Smax] buffer:
         pointer and row stride depend on the state only, so one graph serves every max_new_tokens of the bucket."""
-        gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")))
+        gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")), self.kv_cache_dtype)
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

@@ -432,6 +432,40 @@ def attention_decode_workspace(B, Hq, hd, max_splits) -> int:
     return int(lib().gar_attention_decode_workspace(B, Hq, hd, max_splits))
 
 
+# ---- FP8 KV cache (include/gar_hip.h, ABI 16): Kc8 / Vc8 uint8 [B, Hkv, Smax, hd], Ks / Vs float32 [B, Hkv, Smax]
+def kv_quantize_fp8(K, V, Kc8, Vc8, Ks, Vs, B, Hkv, hd, Smax, S, kv_start: int = 0):
+    """``K`` / ``V`` [B, Hkv, src_stride, hd] 16-bit -> rows kv_start .. S - 1 of the fp8 cache and its scale planes."""
+    for t, n in ((K, "K"), (V, "V"), (Kc8, "Kc8"), (Vc8, "Vc8"), (Ks, "Ks"), (Vs, "Vs")):
+        _chk(t, f"kv_quantize_fp8 {n}")
+    _timed("kv_quantize_fp8", B * Hkv * (S - kv_start) * (hd * 2 * 2 + hd * 2 + 8), lambda: check(
+        lib(K.dtype).gar_kv_quantize_fp8(dtype_code(K.dtype), ptr(K), ptr(V), int(K.shape[2]), ptr(Kc8), ptr(Vc8), ptr(Ks), ptr(Vs),
+                                         B, Hkv, hd, Smax, int(kv_start), int(S), stream()), "gar_kv_quantize_fp8"))
+
+
+def attention_decode_fp8(q, Kc8, Vc8, Ks, Vs, O, B, Hq, Hkv, hd, Smax, kv_len_dev, max_splits, workspace, kv_start=None,
+                         q_stride: int = 0):
+    """attention_decode over the fp8 cache (same arguments, plus the scale planes)."""
+    _timed("attn_decode_fp8", 0.0, lambda: check(
+        lib(q.dtype).gar_attention_decode_fp8(dtype_code(q.dtype), ptr(q), int(q_stride), ptr(Kc8), ptr(Vc8), ptr(Ks), ptr(Vs), ptr(O),
+                                              B, Hq, Hkv, hd, Smax, ptr(kv_len_dev), ptr(kv_start), max_splits, ptr(workspace),
+                                              stream()), "gar_attention_decode_fp8"))
+
+
+def attention_decode_qkv_fp8(qkv, cos, sin, Kc8, Vc8, Ks, Vs, O, B, Hq, Hkv, hd, Smax, pos_dev, q_scale, max_splits, workspace,
+                             left_pad=None, strip_order: bool = False):
+    """attention_decode_qkv over the fp8 cache: the new key / value rows are quantized and appended (with their scales) at row
+    pos_dev[0]. Raises for float32 (the fp8 cache has no parity mode)."""
+    _timed("attn_decode_fp8", 0.0, lambda: check(
+        lib(qkv.dtype).gar_attention_decode_qkv_fp8(dtype_code(qkv.dtype), ptr(qkv), ptr(cos), ptr(sin), ptr(Kc8), ptr(Vc8), ptr(Ks),
+                                                    ptr(Vs), ptr(O), B, Hq, Hkv, hd, Smax, ptr(pos_dev), ptr(left_pad), q_scale,
+                                                    int(strip_order), max_splits, ptr(workspace), stream()),
+        "gar_attention_decode_qkv_fp8"))
+
+
+def attention_decode_fp8_workspace(B, Hq, hd, max_splits) -> int:
+    return int(lib().gar_attention_decode_fp8_workspace(B, Hq, hd, max_splits))
+
+
 def pool2x2(x, y, g: int, in_tile_tokens: int = 0, in_token_offset: int = 0):
     """x [T, in_tile_tokens, C] (tokens in_token_offset .. +g*g of each tile are the g x g grid) -> y [T, (g/2)^2, C]"""
     T, Cc = y.shape[0], y.shape[-1]

@@ -38,7 +38,7 @@ extern "C" {
 #define GAR_F32 0
 #define GAR_BF16 1
 
-#define GAR_ABI_VERSION 15
+#define GAR_ABI_VERSION 16
 
 /* GEMM epilogues */
 #define GAR_EPI_NONE 0            /* C = A W^T                                               */
@@ -270,6 +270,35 @@ int gar_attention_decode(int dtype, const void* q, int64_t q_stride, const void*
 int gar_attention_decode_qkv(int dtype, const void* qkv, const float* cos, const float* sin, void* Kc, void* Vc, void* O,
                              int B, int Hq, int Hkv, int hd, int Smax, const int32_t* pos_dev, const int32_t* left_pad,
                              float q_scale, int qk_strip_order, int max_splits, void* workspace, gar_stream_t stream);
+
+/* ---- FP8 KV cache (ABI 16; GARModel(kv_cache_dtype="fp8")) ----------------------------------------------------------------
+ * What these replace: HF's DynamicCache.update plus the attention of one greedy step (modeling_gar.py:418-426), with the cache
+ * held as OCP e4m3fn bytes instead of the model dtype. Kc8 / Vc8 uint8 [B,Hkv,Smax,hd]; Ks / Vs f32 [B,Hkv,Smax]: one scale per
+ * (sequence, kv head, position), K and V apart. A 16-bit vector x (hd values; K after RoPE) is stored as
+ *     amax = max|x|, inv = 448 / amax, q = e4m3(RNE(x * inv)), scale = amax / 448
+ * and as q = 0, scale = 0 where inv is not finite (amax == 0, or amax < 448 / FLT_MAX ~ 1.3e-36, which bf16 can hold)
+ * in exactly these f32 operations ((x.float() * inv).to(torch.float8_e4m3fn) restates them byte for byte). The decode kernels
+ * dequantize by scaling: score_j = (q . k8_j) * sk_j, and p_j * sv_j enters the PV product (the softmax is unchanged).
+ * 16-bit types only (dtype GAR_BF16 — bf16, or fp16 in the twin library); head_dim 64 / 128; GAR_F32 is refused.
+ *
+ * gar_kv_quantize_fp8: K, V [B,Hkv,src_stride,hd] 16-bit (a prefill's per-layer scratch) -> rows kv_start .. S - 1 of
+ * Kc8 / Vc8 / Ks / Vs. One wave per (position, kv head, sequence). */
+int gar_kv_quantize_fp8(int dtype, const void* K, const void* V, int src_stride, void* Kc8, void* Vc8, float* Ks, float* Vs,
+                        int B, int Hkv, int hd, int Smax, int kv_start, int S, gar_stream_t stream);
+/* gar_attention_decode over the fp8 cache: the same contract (split-KV, GQA heads as MFMA columns, device kv_len, kv_start
+ * for left-padded rows, q_stride, gar_attention_decode's combine), K / V tiles and their scales DMA-staged at half the bytes.
+ * workspace >= gar_attention_decode_fp8_workspace() bytes. Smax * hd < 2 GiB (GAR_ERR_UNSUPPORTED otherwise). */
+int64_t gar_attention_decode_fp8_workspace(int B, int Hq, int hd, int max_splits);
+int gar_attention_decode_fp8(int dtype, const void* q, int64_t q_stride, const void* Kc8, const void* Vc8, const float* Ks,
+                             const float* Vs, void* O, int B, int Hq, int Hkv, int hd, int Smax, const int32_t* kv_len_dev,
+                             const int32_t* kv_start, int max_splits, void* workspace, gar_stream_t stream);
+/* gar_attention_decode_qkv over the fp8 cache, one launch: RoPE + q_scale on the query heads, the new key rotated and rounded to
+ * the 16-bit type, key and value quantized as gar_kv_quantize_fp8 does and appended with their scales at row pos_dev[0], then
+ * the attention over rows left_pad[b] .. pos_dev[0]. */
+int gar_attention_decode_qkv_fp8(int dtype, const void* qkv, const float* cos, const float* sin, void* Kc8, void* Vc8, float* Ks,
+                                 float* Vs, void* O, int B, int Hq, int Hkv, int hd, int Smax, const int32_t* pos_dev,
+                                 const int32_t* left_pad, float q_scale, int qk_strip_order, int max_splits, void* workspace,
+                                 gar_stream_t stream);
 
 /* PerceptionLMAdaptiveAvgPooling (modeling_perception_lm.py:47-60): per tile [g*g, C] -> [(g/2)^2, C], exact 2x2
  * mean. Input tile t starts at row t*in_tile_tokens + in_token_offset of x (lets the projector run over the
