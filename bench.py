@@ -12,8 +12,12 @@ region starts. Weights: seeded synthetic GAR-1B (no checkpoint is reachable offl
 
 One JSON line on rank 0 (see DESIGN.md "Measurement"): value = N*K*B / max-over-ranks wall time; `roofline` = the
 dominant kernel (bf16 tile GEMM: ViT + projector + prefill) timed live with HIP events on the launch stream over the
-timed region; `cpu_baseline` = the fp32 CPU oracle on a bounded sample of the same workload on this box's cores.
-`ms_per_step` = milliseconds of one of the K timed steps.
+timed region. `ms_per_step` = milliseconds of one of the K timed steps.
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` also runs, after the timed region, what
+takes runs of its own: the eager decode probe (the decode kernels' `roofline_other` entries, `decode_step_probe`), one
+more batch for `decode_loop`, and at N = 1 `cpu_baseline` = the fp32 CPU oracle on a bounded sample of the same workload
+on the host's cores. The timed steps are the same either way.
 
 `--dump-outputs DIR` writes what the last timed step returned (the caption ids gathered on rank 0) as DIR/sequences.npy;
 the inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
@@ -84,9 +88,12 @@ def parse(argv=None):
     ap.add_argument("--runtime", default=None,
                     help="module:attr of a runtime object replacing GpuRuntime (tests/bench_stub.py: a CPU stub under gloo, so that "
                          "the N > 1 control flow and the self-launch run on a box without GPUs); never set for a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline figure does not need: the eager decode probe, one "
+                         "more batch for decode_loop and (N = 1) the fp32 CPU oracle's cpu_baseline; off by default")
     ap.add_argument("--decode-probe-steps", type=int, default=2,
-                    help="eager decode steps timed kernel by kernel AFTER the timed region (rank 0) for the roofline_other entries of "
-                         "the kernels that run inside the hipGraph during it (decode attention, decode GEMVs); 0 = off")
+                    help="--full: eager decode steps timed kernel by kernel AFTER the timed region (rank 0) for the roofline_other "
+                         "entries of the kernels that run inside the hipGraph during it (decode attention, decode GEMVs); 0 = off")
     ap.add_argument("--vit-chunk-rows", type=int, default=0, help="A/B: cap on the token rows of one vision-tower pass (GARModel.VIT_CHUNK_ROWS)")
     ap.add_argument("--prefill-chunk-rows", type=int, default=0, help="A/B: cap on the rows of one prefill pass (GARModel.PREFILL_CHUNK_ROWS)")
     ap.add_argument("--no-prune-last-layer", action="store_true",
@@ -102,7 +109,7 @@ def parse(argv=None):
     ap.add_argument("--eos-mix-admit-min", type=int, default=0,
                     help="--eos-mix: free rows the continuous batcher waits for before it runs a prompt phase (0 = its default, slots / 4)")
     ap.add_argument("--eos-mix-poll", type=int, default=8, help="--eos-mix: decode steps between two polls of the finished latches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (rank 0: the caption ids of every rank, "
@@ -660,7 +667,7 @@ def main(argv=None, runtime=None):
     # ---- kernels that run inside the hipGraph during the timed region (decode attention, decode GEMVs, split-K reduce):
     # a few EAGER decode steps of the same batch after it, every launch bracketed by HIP events (rank 0)
     probe = []
-    if args.decode_probe_steps > 0 and args.new_tokens > 1 and hasattr(model, "generate_finish"):
+    if args.full and args.decode_probe_steps > 0 and args.new_tokens > 1 and hasattr(model, "generate_finish"):
         ops.KERNEL_TIMERS = []
         model.generate(**make_batch(0), **{**gen_kw, "max_new_tokens": args.decode_probe_steps + 1, "use_graph": False})
         rt.sync()
@@ -668,7 +675,7 @@ def main(argv=None, runtime=None):
     # ---- the decode loop by itself (what the reference's callers wait for per token at batch 1): one more generate after the
     # timed region, host clock around generate_finish() only — the hipGraph replays of new_tokens - 1 steps
     decode_loop = None
-    if args.new_tokens > 1 and hasattr(model, "generate_finish"):
+    if args.full and args.new_tokens > 1 and hasattr(model, "generate_finish"):
         pend = model.generate_begin(**make_batch(0), **gen_kw)
         rt.sync()
         td = time.perf_counter()
@@ -847,10 +854,11 @@ def main(argv=None, runtime=None):
         line["decode_loop"] = decode_loop
     covered = sum(v.get("time_share_of_step", 0.0) for k, v in other.items() if not k.startswith("roi_replay_inplace_kernel alone"))
     line["time_share_covered"] = (roof["time_share_of_step"] if roof else 0.0) + covered
-    if not args.no_cpu_baseline and world == 1 and args.workload == "video":
+    run_cpu_baseline = args.full and not args.no_cpu_baseline and world == 1       # reported on rank 0 at N=1 only
+    if run_cpu_baseline and args.workload == "video":
         line["cpu_baseline"] = {"value": None, "note": "the CPU oracle leg is wired for the image workloads (run "
                                                        "--workload single for the headline line's baseline)"}
-    elif not args.no_cpu_baseline and world == 1:        # reported on rank 0 at N=1 only
+    elif run_cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline(cfg, W, one, args.new_tokens, args.cpu_threads)
         except Exception as e:  # the baseline is a reported number, never a reason to lose the GPU result
@@ -859,4 +867,8 @@ def main(argv=None, runtime=None):
 
 
 if __name__ == "__main__":
-    main()
+    try:
+        main()
+    finally:        # a process group left to the interpreter's teardown can abort a rank after its work is done
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()

@@ -167,3 +167,49 @@ def test_dry_run_prints_the_launch_plan():
     assert [r["device"] for r in d["ranks"]] == [f"cuda:{i}" for i in range(8)]
     assert d["ranks"][5]["regions"].startswith("i % 8 == 5: 5, 13, 21")
     assert d["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_plain_run_skips_what_full_adds(monkeypatch, capsys):
+    """A plain run (CPU stub, one rank) prints the headline line after the warm-up and the K timed steps and starts nothing
+    else; `--full` adds the eager decode probe, the extra decode-loop batch and the CPU oracle's cpu_baseline after them."""
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    for p in (ROOT, os.path.join(ROOT, "grasp-any-region_amd"), os.path.join(ROOT, "tests")):
+        monkeypatch.syspath_prepend(p)
+    import bench
+    import bench_stub
+
+    class Model(bench_stub.StubModel):         # the decode-loop surface GARModel has and the plain stub does not
+        layers = []
+        lm_head = torch.zeros(4, 4)
+
+        def generate_begin(self, **kw):
+            return self.generate(**kw)
+
+        def generate_finish(self, pending):
+            return pending
+
+    class Runtime(bench_stub.StubRuntime):
+        def build_model(self, args, cfg, rank, device):
+            return Model(rank), None
+
+    baselines = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a: baselines.append(a) or {"value": 1.0})
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "2", "--new-tokens", "4", "--model", "tiny",
+            "--max-num-tiles", "4"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        bench_stub.LOG["generate_calls"] = 0
+        bench.main(argv + extra, runtime=Runtime())
+        out = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines[name] = (json.loads(out[0]), bench_stub.LOG["generate_calls"])
+    plain, n_plain = lines["plain"]
+    full, n_full = lines["full"]
+    assert n_plain == 2 + 3 and n_full == 2 + 3 + 2                 # --full: + the decode probe + the decode-loop batch
+    assert len(baselines) == 1
+    assert not {"cpu_baseline", "decode_loop"} & set(plain)
+    assert full["cpu_baseline"] == {"value": 1.0} and full["decode_loop"]["steps"] == 3
+    for d in (plain, full):
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["unit"] == "regions/s" and d["higher_is_better"]
+        assert abs(d["value"] - 3 * 2 / (d["ms_per_step"] * 3 / 1e3)) < 1e-6 * d["value"]
