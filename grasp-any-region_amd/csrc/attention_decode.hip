@@ -13,7 +13,6 @@
 
 #include "common.h"
 
-typedef float f32v2_d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned int cvt_pk_d(float lo, float hi) { return pack_bf2(lo, hi); }
 
 typedef short tr4_d __attribute__((ext_vector_type(4)));
@@ -108,6 +107,68 @@ __device__ __forceinline__ void append_new_kv(const decode_qkv_args& fa, bf16_t*
         *reinterpret_cast<uint4*>(vs + r * RB + ((lane ^ vkey(r)) << 4)) = w;
     }
     asm volatile("" ::: "memory");          // the fragment reads that follow (ds_read / transposing reads) stay behind the patch
+}
+
+// merge the four waves in LDS (red = [4 waves][8 heads][HD + 2] f32) into the block's partial (m, l, O[G][HD]) in `part`; with a
+// single split (O_direct set) that partial, normalised, IS the result (what decode_combine_kernel computes for nsplit = 1)
+template <int HD>
+__device__ __forceinline__ void merge_waves_store(const f32x16 (&o)[HD / 32], float m_run, float l_run, float (*red)[8][HD + 2],
+                                                  float* __restrict__ part, bf16_t* __restrict__ O_direct, int tid, int wave,
+                                                  int l31, int h, int b, int Hq, int Hkv, int kvh, int G, int split, int nsplit) {
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (l31 < G) {
+        float* pp = &red[wave][l31][0];
+#pragma unroll
+        for (int d = 0; d < HD / 32; ++d)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pp[d * 32 + g4 * 8 + h * 4 + e] = o[d][g4 * 4 + e];
+        if (h == 0) { pp[HD] = m_run; pp[HD + 1] = l_tot; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < G * HD; idx += 256) {
+        const int g = idx / HD, d = idx % HD;
+        float m = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) m = fmaxf(m, red[w][g][HD]);
+        const float m_use = m == -INFINITY ? 0.f : m;
+        float acc = 0.f, l = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float sc = __builtin_amdgcn_exp2f(red[w][g][HD] - m_use);
+            acc += sc * red[w][g][d];
+            l += sc * red[w][g][HD + 1];
+        }
+        if (O_direct) {
+            const float inv = l > 0.f ? 1.0f / l : 0.f;
+            O_direct[((int64_t)b * Hq + kvh * G + g) * HD + d] = f2bf(acc * inv);
+            continue;
+        }
+        float* pp = part + ((((int64_t)b * Hkv + kvh) * nsplit + split) * G + g) * (HD + 2);
+        pp[d] = acc;
+        if (d == 0) { pp[HD] = m; pp[HD + 1] = l; }
+    }
+}
+
+struct identity_d {
+    template <class T, class... I>
+    __device__ T operator()(T x, I...) const { return x; }
+};
+// O = alpha O + V^T P: vf[d][c4] = the A operand of d block d, kv 16 c4 .. +15, made 16-bit by `cvt`
+template <int NDB, class VF, class CV = identity_d>
+__device__ __forceinline__ void pv_update(f32x16 (&o)[NDB], const VF (&vf)[NDB][4], const bf16x8 (&pf)[2][2], float alpha,
+                                          CV cvt = CV()) {
+#pragma unroll
+    for (int d = 0; d < NDB; ++d) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+                o[d] = MFMA_32x32x16(cvt(vf[d][blk * 2 + tt]), pf[blk][tt], o[d]);
+    }
 }
 
 #ifndef DA_KV_AUX               /* cache policy of the K / V DMA: 2 = nt — every byte of the cache is read once per step:
@@ -260,52 +321,9 @@ __global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* _
             }
         }
         l_run = l_run * alpha + ps;
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-                    o[d] = MFMA_32x32x16(vf[d][blk * 2 + tt], pf[blk][tt], o[d]);
-        }
+        pv_update(o, vf, pf, alpha);
     }
-    // ---- merge the four waves (LDS), one partial per block
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (l31 < G) {
-        float* pp = &red[wave][l31][0];
-#pragma unroll
-        for (int d = 0; d < NDB; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pp[d * 32 + g4 * 8 + h * 4 + e] = o[d][g4 * 4 + e];
-        if (h == 0) { pp[HD] = m_run; pp[HD + 1] = l_tot; }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < G * HD; idx += 256) {
-        const int g = idx / HD, d = idx % HD;
-        float m = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) m = fmaxf(m, red[w][g][HD]);
-        const float m_use = m == -INFINITY ? 0.f : m;
-        float acc = 0.f, l = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __builtin_amdgcn_exp2f(red[w][g][HD] - m_use);
-            acc += sc * red[w][g][d];
-            l += sc * red[w][g][HD + 1];
-        }
-        if (O_direct) {      // a single split: this IS the result (what decode_combine_kernel computes for nsplit = 1)
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            O_direct[((int64_t)b * Hq + kvh * G + g) * HD + d] = f2bf(acc * inv);
-            continue;
-        }
-        float* pp = part + ((((int64_t)b * Hkv + kvh) * nsplit + split) * G + g) * (HD + 2);
-        pp[d] = acc;
-        if (d == 0) { pp[HD] = m; pp[HD + 1] = l; }
-    }
+    merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, b, Hq, Hkv, kvh, G, split, nsplit);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -479,52 +497,9 @@ __global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t
         __builtin_amdgcn_sched_barrier(0);
         if (more) stageV(t + 4);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-                    o[d] = MFMA_32x32x16(vf[d][blk * 2 + tt], pf[blk][tt], o[d]);
-        }
+        pv_update(o, vf, pf, alpha);
     }
-    // ---- merge the four waves (LDS), one partial per block — as in decode_attn_lds_kernel
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (l31 < G) {
-        float* pp = &red[wave][l31][0];
-#pragma unroll
-        for (int d = 0; d < NDB; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pp[d * 32 + g4 * 8 + h * 4 + e] = o[d][g4 * 4 + e];
-        if (h == 0) { pp[HD] = m_run; pp[HD + 1] = l_tot; }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < G * HD; idx += 256) {
-        const int g = idx / HD, d = idx % HD;
-        float m = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) m = fmaxf(m, red[w][g][HD]);
-        const float m_use = m == -INFINITY ? 0.f : m;
-        float acc = 0.f, l = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __builtin_amdgcn_exp2f(red[w][g][HD] - m_use);
-            acc += sc * red[w][g][d];
-            l += sc * red[w][g][HD + 1];
-        }
-        if (O_direct) {      // a single split: this IS the result (what decode_combine_kernel computes for nsplit = 1)
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            O_direct[((int64_t)b * Hq + kvh * G + g) * HD + d] = f2bf(acc * inv);
-            continue;
-        }
-        float* pp = part + ((((int64_t)b * Hkv + kvh) * nsplit + split) * G + g) * (HD + 2);
-        pp[d] = acc;
-        if (d == 0) { pp[HD] = m; pp[HD + 1] = l; }
-    }
+    merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, b, Hq, Hkv, kvh, G, split, nsplit);
 }
 
 // one wave per (b, q head): lanes over splits for the statistics, then over d for the accumulation
@@ -559,64 +534,75 @@ extern "C" int64_t gar_attention_decode_workspace(int B, int Hq, int hd, int max
     return (int64_t)B * Hq * max_splits * (hd + 2) * 4;
 }
 
-static int launch_decode(const void* q, int64_t q_stride, void* Kc, void* Vc, void* O, int B, int Hq, int Hkv, int hd, int Smax,
-                         const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits, void* workspace,
-                         const decode_qkv_args& fa, gar_stream_t stream) {
-    GAR_CHECK_ARG(workspace && max_splits > 0 && max_splits <= 64, "attention_decode: workspace / max_splits (1..64)");
-    if ((int64_t)Smax * hd * 2 >= ((int64_t)1 << 31)) {       // one (sequence, kv head) slab has to fit a buffer descriptor
-        gar_set_error("attention_decode: Smax %d x head_dim %d exceeds the 2 GiB per-slab range of the DMA-staged kernels", Smax, hd);
+// the argument checks every decode entry point shares (`what`: the entry point, for the error text). Plain forms: q and its
+// row stride (<= 0 means head_dim). Fused forms: q = the raw qkv rows, q_stride null.
+static int check_decode_args(const char* what, const void* q, int64_t* q_stride, int B, int Hq, int Hkv, int hd, int Smax) {
+    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "%s: Hq/Hkv must be <= 8", what);
+    GAR_CHECK_ARG(Smax % 64 == 0, "%s: Smax must be a multiple of 64", what);
+    GAR_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d not built (64, 128)", what, hd);
+    if (!q_stride) {
+        GAR_CHECK_ARG(((uintptr_t)q & 15) == 0, "%s: qkv must be 16-byte aligned", what);
+        return GAR_OK;
+    }
+    int64_t& qs = *q_stride;
+    if (qs <= 0) qs = hd;
+    GAR_CHECK_ARG(qs % hd == 0 && ((uintptr_t)q & 15) == 0, "%s: q_stride must be a multiple of head_dim, q 16-byte aligned", what);
+    return GAR_OK;
+}
+
+// dynamic LDS of a decode block: the four waves' tile regions, then the merge buffer red[4 waves][8 heads][HD + 2] f32
+constexpr int decode_lds_bytes(int wave_bytes, int hd) { return 4 * wave_bytes + 4 * 8 * (hd + 2) * 4; }
+
+// one split-KV decode: KERNEL (LDS bytes of dynamic LDS) on the grid (max_splits, Hkv, B), then decode_combine_kernel — with
+// one split per (sequence, kv head) the attention kernel normalises and writes O itself, no combine launch. `caches`: the
+// kernel's cache pointer arguments, `elem_bytes` the bytes of one cache element.
+template <int HD, auto KERNEL, int LDS, class... Caches>
+static int launch_split_kv(const char* what, int elem_bytes, const void* q, int64_t q_stride, void* O, int B, int Hq, int Hkv,
+                           int Smax, const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits, void* workspace,
+                           const decode_qkv_args& fa, gar_stream_t stream, Caches... caches) {
+    GAR_CHECK_ARG(workspace && max_splits > 0 && max_splits <= 64, "%s: workspace / max_splits (1..64)", what);
+    if ((int64_t)Smax * HD * elem_bytes >= ((int64_t)1 << 31)) {       // one (sequence, kv head) slab has to fit a buffer descriptor
+        gar_set_error("%s: Smax %d x head_dim %d exceeds the 2 GiB per-slab range of the DMA-staged kernels", what, Smax, HD);
         return GAR_ERR_UNSUPPORTED;
     }
+    static gar_once_per_device attr_once;
+    attr_once.run([&] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    });
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid(max_splits, Hkv, B);
-    // one split per (sequence, kv head): the attention kernel normalises and writes O itself, no combine launch
     bf16_t* direct = max_splits == 1 ? (bf16_t*)O : nullptr;
-    if (hd == 64) {
-        constexpr int lds = 4 * 16384 + 4 * 8 * (64 + 2) * 4;
-        static gar_once_per_device attr_once;
-        attr_once.run([&] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_lds_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        hipLaunchKernelGGL(decode_attn_lds_kernel, grid, dim3(256), lds, s, (const bf16_t*)q, (bf16_t*)Kc,
-                           (bf16_t*)Vc, (float*)workspace, Hq, Hkv, Smax, kv_len_dev, kv_start, direct, fa, q_stride);
-        if (!direct)
-            hipLaunchKernelGGL((decode_combine_kernel<64>), dim3(Hq, B), dim3(64), 0, s, (const float*)workspace,
-                               (bf16_t*)O, Hq, Hkv, max_splits);
-    } else {
-        constexpr int lds = 4 * 32768 + 4 * 8 * (128 + 2) * 4;
-        static gar_once_per_device attr_once;
-        attr_once.run([&] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_lds128_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        hipLaunchKernelGGL(decode_attn_lds128_kernel, grid, dim3(256), lds, s, (const bf16_t*)q, (bf16_t*)Kc,
-                           (bf16_t*)Vc, (float*)workspace, Hq, Hkv, Smax, kv_len_dev, kv_start, direct, fa, q_stride);
-        if (!direct)
-            hipLaunchKernelGGL((decode_combine_kernel<128>), dim3(Hq, B), dim3(64), 0, s, (const float*)workspace,
-                               (bf16_t*)O, Hq, Hkv, max_splits);
-    }
+    hipLaunchKernelGGL(KERNEL, dim3(max_splits, Hkv, B), dim3(256), LDS, s, (const bf16_t*)q, caches..., (float*)workspace, Hq, Hkv,
+                       Smax, kv_len_dev, kv_start, direct, fa, q_stride);
+    if (!direct)
+        hipLaunchKernelGGL((decode_combine_kernel<HD>), dim3(Hq, B), dim3(64), 0, s, (const float*)workspace, (bf16_t*)O, Hq, Hkv,
+                           max_splits);
     GAR_CHECK_LAUNCH();
     return GAR_OK;
+}
+
+static int launch_decode(const char* what, const void* q, int64_t q_stride, void* Kc, void* Vc, void* O, int B, int Hq, int Hkv,
+                         int hd, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits, void* workspace,
+                         const decode_qkv_args& fa, gar_stream_t stream) {
+    if (hd == 64)
+        return launch_split_kv<64, decode_attn_lds_kernel, decode_lds_bytes(16384, 64)>(
+            what, 2, q, q_stride, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, stream, (bf16_t*)Kc, (bf16_t*)Vc);
+    return launch_split_kv<128, decode_attn_lds128_kernel, decode_lds_bytes(32768, 128)>(
+        what, 2, q, q_stride, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, stream, (bf16_t*)Kc, (bf16_t*)Vc);
 }
 
 extern "C" int gar_attention_decode(int dtype, const void* q, int64_t q_stride, const void* Kc, const void* Vc, void* O, int B,
                                     int Hq, int Hkv, int hd, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start,
                                     int max_splits, void* workspace, gar_stream_t stream) {
     GAR_CHECK_ARG(q && Kc && Vc && O && kv_len_dev, "attention_decode: null pointer");
-    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "attention_decode: Hq/Hkv must be <= 8");
-    GAR_CHECK_ARG(Smax % 64 == 0, "attention_decode: Smax must be a multiple of 64");
-    GAR_CHECK_ARG(hd == 64 || hd == 128, "attention_decode: head_dim %d not built (64, 128)", hd);
-    if (q_stride <= 0) q_stride = hd;
-    GAR_CHECK_ARG(q_stride % hd == 0 && ((uintptr_t)q & 15) == 0, "attention_decode: q_stride must be a multiple of head_dim, q 16-byte aligned");
+    if (int e = check_decode_args("attention_decode", q, &q_stride, B, Hq, Hkv, hd, Smax)) return e;
     if (dtype == GAR_F32)   // parity mode: the prefill kernel with q_len = 1 (exact-f32 MFMA), no split; (b, head) rows q_stride apart
         return gar_attention_vrow(dtype, q, Kc, Vc, O, B, Hq, Hkv, hd, 1, (int)(q_stride / hd), 0, Smax, 0, kv_len_dev, kv_start, 0,
                                   stream);
     GAR_CHECK_ARG(dtype == GAR_BF16, "attention_decode: bad dtype");
     const decode_qkv_args none = {nullptr, nullptr, nullptr, 0.f, 0};
     // (the plain form only reads the caches)
-    return launch_decode(q, q_stride, const_cast<void*>(Kc), const_cast<void*>(Vc), O, B, Hq, Hkv, hd, Smax, kv_len_dev, kv_start,
-                         max_splits, workspace, none, stream);
+    return launch_decode("attention_decode", q, q_stride, const_cast<void*>(Kc), const_cast<void*>(Vc), O, B, Hq, Hkv, hd, Smax,
+                         kv_len_dev, kv_start, max_splits, workspace, none, stream);
 }
 
 // gar_llm_qkv_post (S = 1) + gar_attention_decode in ONE launch (bf16): see decode_qkv_args. GAR_ERR_UNSUPPORTED (nothing
@@ -626,16 +612,14 @@ extern "C" int gar_attention_decode_qkv(int dtype, const void* qkv, const float*
                                         const int32_t* left_pad, float q_scale, int qk_strip_order, int max_splits,
                                         void* workspace, gar_stream_t stream) {
     GAR_CHECK_ARG(qkv && cos && sin && Kc && Vc && O && pos_dev, "attention_decode_qkv: null pointer");
-    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "attention_decode_qkv: Hq/Hkv must be <= 8");
-    GAR_CHECK_ARG(Smax % 64 == 0, "attention_decode_qkv: Smax must be a multiple of 64");
-    GAR_CHECK_ARG(hd == 64 || hd == 128, "attention_decode_qkv: head_dim %d not built (64, 128)", hd);
-    GAR_CHECK_ARG(((uintptr_t)qkv & 15) == 0, "attention_decode_qkv: qkv must be 16-byte aligned");
+    if (int e = check_decode_args("attention_decode_qkv", qkv, nullptr, B, Hq, Hkv, hd, Smax)) return e;
     if (dtype != GAR_BF16) {
         gar_set_error("attention_decode_qkv: bf16 only (parity mode runs gar_llm_qkv_post + gar_attention_decode)");
         return GAR_ERR_UNSUPPORTED;
     }
     const decode_qkv_args fa = {(const bf16_t*)qkv, cos, sin, q_scale, qk_strip_order ? 1 : 0};
-    return launch_decode(nullptr, hd, Kc, Vc, O, B, Hq, Hkv, hd, Smax, pos_dev, left_pad, max_splits, workspace, fa, stream);
+    return launch_decode("attention_decode_qkv", nullptr, hd, Kc, Vc, O, B, Hq, Hkv, hd, Smax, pos_dev, left_pad, max_splits,
+                         workspace, fa, stream);
 }
 
 // =====================================================================================================================
@@ -1005,89 +989,23 @@ __global__ __launch_bounds__(256, HD == 64 ? 2 : 1) void decode_attn_fp8_kernel(
             }
         }
         l_run = l_run * alpha + ps;
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-                    o[d] = MFMA_32x32x16(fp8x8_to_h16(vr[d][blk * 2 + tt]), pf[blk][tt], o[d]);
-        }
+        pv_update(o, vr, pf, alpha, [](u32x2 w) { return fp8x8_to_h16(w); });
     }
-    // ---- merge the four waves (LDS), one partial per block — as in decode_attn_lds_kernel
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    if (l31 < G) {
-        float* pp = &red[wave][l31][0];
-#pragma unroll
-        for (int d = 0; d < NDB; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pp[d * 32 + g4 * 8 + h * 4 + e] = o[d][g4 * 4 + e];
-        if (h == 0) { pp[HD] = m_run; pp[HD + 1] = l_tot; }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < G * HD; idx += 256) {
-        const int g = idx / HD, d = idx % HD;
-        float m = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) m = fmaxf(m, red[w][g][HD]);
-        const float m_use = m == -INFINITY ? 0.f : m;
-        float acc = 0.f, l = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __builtin_amdgcn_exp2f(red[w][g][HD] - m_use);
-            acc += sc * red[w][g][d];
-            l += sc * red[w][g][HD + 1];
-        }
-        if (O_direct) {
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            O_direct[((int64_t)b * Hq + kvh * G + g) * HD + d] = f2bf(acc * inv);
-            continue;
-        }
-        float* pp = part + ((((int64_t)b * Hkv + kvh) * nsplit + split) * G + g) * (HD + 2);
-        pp[d] = acc;
-        if (d == 0) { pp[HD] = m; pp[HD + 1] = l; }
-    }
+    merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, b, Hq, Hkv, kvh, G, split, nsplit);
 }
 
-template <int HD>
-static void launch_decode_fp8_hd(const void* q, int64_t q_stride, void* K8, void* V8, float* Ks, float* Vs, void* O, int B, int Hq,
-                                 int Hkv, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits,
-                                 void* workspace, const decode_qkv_args& fa, hipStream_t s) {
-    constexpr int lds = 4 * (4 * 64 * HD + 3 * 512) + 4 * 8 * (HD + 2) * 4;
-    static gar_once_per_device attr_once;
-    attr_once.run([&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_fp8_kernel<HD>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
-    bf16_t* direct = max_splits == 1 ? (bf16_t*)O : nullptr;
-    hipLaunchKernelGGL(decode_attn_fp8_kernel<HD>, dim3(max_splits, Hkv, B), dim3(256), lds, s, (const bf16_t*)q, (uint8_t*)K8,
-                       (uint8_t*)V8, Ks, Vs, (float*)workspace, Hq, Hkv, Smax, kv_len_dev, kv_start, direct, fa, q_stride);
-    if (!direct)
-        hipLaunchKernelGGL((decode_combine_kernel<HD>), dim3(Hq, B), dim3(64), 0, s, (const float*)workspace, (bf16_t*)O, Hq, Hkv,
-                           max_splits);
-}
-
-static int launch_decode_fp8(const void* q, int64_t q_stride, void* K8, void* V8, float* Ks, float* Vs, void* O, int B, int Hq,
-                             int Hkv, int hd, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start, int max_splits,
-                             void* workspace, const decode_qkv_args& fa, gar_stream_t stream) {
-    GAR_CHECK_ARG(workspace && max_splits > 0 && max_splits <= 64, "attention_decode_fp8: workspace / max_splits (1..64)");
+static int launch_decode_fp8(const char* what, const void* q, int64_t q_stride, void* K8, void* V8, float* Ks, float* Vs, void* O,
+                             int B, int Hq, int Hkv, int hd, int Smax, const int32_t* kv_len_dev, const int32_t* kv_start,
+                             int max_splits, void* workspace, const decode_qkv_args& fa, gar_stream_t stream) {
     GAR_CHECK_ARG(((uintptr_t)K8 & 15) == 0 && ((uintptr_t)V8 & 15) == 0 && ((uintptr_t)Ks & 15) == 0 && ((uintptr_t)Vs & 15) == 0,
-                  "attention_decode_fp8: caches and scale planes must be 16-byte aligned");
-    if ((int64_t)Smax * hd >= ((int64_t)1 << 31)) {
-        gar_set_error("attention_decode_fp8: Smax %d x head_dim %d exceeds the 2 GiB per-slab range of the DMA-staged kernel", Smax, hd);
-        return GAR_ERR_UNSUPPORTED;
-    }
-    hipStream_t s = (hipStream_t)stream;
+                  "%s: caches and scale planes must be 16-byte aligned", what);
     if (hd == 64)
-        launch_decode_fp8_hd<64>(q, q_stride, K8, V8, Ks, Vs, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, s);
-    else
-        launch_decode_fp8_hd<128>(q, q_stride, K8, V8, Ks, Vs, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, s);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+        return launch_split_kv<64, decode_attn_fp8_kernel<64>, decode_lds_bytes(4 * 64 * 64 + 3 * 512, 64)>(
+            what, 1, q, q_stride, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, stream, (uint8_t*)K8,
+            (uint8_t*)V8, Ks, Vs);
+    return launch_split_kv<128, decode_attn_fp8_kernel<128>, decode_lds_bytes(4 * 64 * 128 + 3 * 512, 128)>(
+        what, 1, q, q_stride, O, B, Hq, Hkv, Smax, kv_len_dev, kv_start, max_splits, workspace, fa, stream, (uint8_t*)K8,
+        (uint8_t*)V8, Ks, Vs);
 }
 
 extern "C" int64_t gar_attention_decode_fp8_workspace(int B, int Hq, int hd, int max_splits) {
@@ -1099,14 +1017,11 @@ extern "C" int gar_attention_decode_fp8(int dtype, const void* q, int64_t q_stri
                                         const int32_t* kv_start, int max_splits, void* workspace, gar_stream_t stream) {
     GAR_CHECK_ARG(q && Kc8 && Vc8 && Ks && Vs && O && kv_len_dev, "attention_decode_fp8: null pointer");
     GAR_CHECK_ARG(dtype == GAR_BF16, "attention_decode_fp8: 16-bit query only (the fp8 cache has no parity mode)");
-    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "attention_decode_fp8: Hq/Hkv must be <= 8");
-    GAR_CHECK_ARG(Smax % 64 == 0, "attention_decode_fp8: Smax must be a multiple of 64");
-    GAR_CHECK_ARG(hd == 64 || hd == 128, "attention_decode_fp8: head_dim %d not built (64, 128)", hd);
-    if (q_stride <= 0) q_stride = hd;
-    GAR_CHECK_ARG(q_stride % hd == 0 && ((uintptr_t)q & 15) == 0, "attention_decode_fp8: q_stride must be a multiple of head_dim, q 16-byte aligned");
+    if (int e = check_decode_args("attention_decode_fp8", q, &q_stride, B, Hq, Hkv, hd, Smax)) return e;
     const decode_qkv_args none = {nullptr, nullptr, nullptr, 0.f, 0};
-    return launch_decode_fp8(q, q_stride, const_cast<void*>(Kc8), const_cast<void*>(Vc8), const_cast<float*>(Ks), const_cast<float*>(Vs),
-                             O, B, Hq, Hkv, hd, Smax, kv_len_dev, kv_start, max_splits, workspace, none, stream);
+    return launch_decode_fp8("attention_decode_fp8", q, q_stride, const_cast<void*>(Kc8), const_cast<void*>(Vc8),
+                             const_cast<float*>(Ks), const_cast<float*>(Vs), O, B, Hq, Hkv, hd, Smax, kv_len_dev, kv_start, max_splits,
+                             workspace, none, stream);
 }
 
 extern "C" int gar_attention_decode_qkv_fp8(int dtype, const void* qkv, const float* cos, const float* sin, void* Kc8, void* Vc8,
@@ -1115,10 +1030,8 @@ extern "C" int gar_attention_decode_qkv_fp8(int dtype, const void* qkv, const fl
                                             int max_splits, void* workspace, gar_stream_t stream) {
     GAR_CHECK_ARG(qkv && cos && sin && Kc8 && Vc8 && Ks && Vs && O && pos_dev, "attention_decode_qkv_fp8: null pointer");
     GAR_CHECK_ARG(dtype == GAR_BF16, "attention_decode_qkv_fp8: 16-bit qkv only (the fp8 cache has no parity mode)");
-    GAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, "attention_decode_qkv_fp8: Hq/Hkv must be <= 8");
-    GAR_CHECK_ARG(Smax % 64 == 0, "attention_decode_qkv_fp8: Smax must be a multiple of 64");
-    GAR_CHECK_ARG(hd == 64 || hd == 128, "attention_decode_qkv_fp8: head_dim %d not built (64, 128)", hd);
-    GAR_CHECK_ARG(((uintptr_t)qkv & 15) == 0, "attention_decode_qkv_fp8: qkv must be 16-byte aligned");
+    if (int e = check_decode_args("attention_decode_qkv_fp8", qkv, nullptr, B, Hq, Hkv, hd, Smax)) return e;
     const decode_qkv_args fa = {(const bf16_t*)qkv, cos, sin, q_scale, qk_strip_order ? 1 : 0};
-    return launch_decode_fp8(nullptr, hd, Kc8, Vc8, Ks, Vs, O, B, Hq, Hkv, hd, Smax, pos_dev, left_pad, max_splits, workspace, fa, stream);
+    return launch_decode_fp8("attention_decode_qkv_fp8", nullptr, hd, Kc8, Vc8, Ks, Vs, O, B, Hq, Hkv, hd, Smax, pos_dev,
+                             left_pad, max_splits, workspace, fa, stream);
 }
