@@ -29,6 +29,9 @@ def base_parser(description):
                     help="resize / tile / normalise on the CPU (torch bicubic) instead of the device kernels")
     ap.add_argument("--kv_cache_dtype", choices=("auto", "fp8"), default="auto",
                     help="decode KV cache: auto = the model dtype; fp8 = OCP e4m3 with one scale per vector (16-bit models only)")
+    ap.add_argument("--decode_weight_dtype", choices=("auto", "fp8"), default="auto",
+                    help="weights of the decode GEMVs: auto = the model dtype; fp8 = OCP e4m3 copies with one scale per output row "
+                         "(16-bit models, decode batches <= 64 rows; the prompt phase keeps 16-bit weights)")
     ap.add_argument("--synthetic_weights", action="store_true",
                     help="seeded random weights of the named size + the stub tokenizer (plumbing / benchmarking)")
     return ap
@@ -40,14 +43,15 @@ def load(args):
     from gar_amd.processing import GARProcessor
     dtype = resolve_data_type(args.data_type)
     kv = None if getattr(args, "kv_cache_dtype", "auto") == "auto" else args.kv_cache_dtype
+    dw = None if getattr(args, "decode_weight_dtype", "auto") == "auto" else args.decode_weight_dtype
     torch.manual_seed(args.seed)
     if args.synthetic_weights:
         name = args.model_name_or_path if args.model_name_or_path in ("gar_1b", "gar_8b", "tiny") else "gar_1b"
         cfg = getattr(GARConfig, name)()
-        model = GARModel.from_synthetic(cfg, args.seed, dtype, args.device, kv_cache_dtype=kv)
+        model = GARModel.from_synthetic(cfg, args.seed, dtype, args.device, kv_cache_dtype=kv, decode_weight_dtype=dw)
         processor = GARProcessor.from_config(cfg, max_num_tiles=args.max_num_tiles)
     else:
-        model = GARModel.from_pretrained(args.model_name_or_path, dtype, args.device, kv_cache_dtype=kv)
+        model = GARModel.from_pretrained(args.model_name_or_path, dtype, args.device, kv_cache_dtype=kv, decode_weight_dtype=dw)
         processor = GARProcessor.from_pretrained(args.model_name_or_path, model.config, args.max_num_tiles)
     if not args.host_preprocessing:
         processor.use_gpu_preprocessing(args.device, dtype)

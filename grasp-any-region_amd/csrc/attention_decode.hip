@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "fp8.h"
 
 __device__ __forceinline__ unsigned int cvt_pk_d(float lo, float hi) { return pack_bf2(lo, hi); }
 
@@ -630,31 +631,7 @@ extern "C" int gar_attention_decode_qkv(int dtype, const void* qkv, const float*
 // in exactly these f32 operations: (x.float() * inv).to(torch.float8_e4m3fn) restates it byte for byte (|x * inv| <= 448
 // rounds inside the format, so the conversion never saturates; the inv = inf case above is excluded, 0 * inf would be NaN). The decode kernels dequantize by scaling, not per element:
 // score_j = (q . k8_j) * sk_j, and the softmax weight p_j enters the PV product as p_j * sv_j (the normaliser sums p_j).
-#define FP8_MAX 448.0f
-
-// four f32 (already times inv) -> four e4m3 bytes, byte i = element i (v_cvt_pk_fp8_f32: round to nearest even)
-__device__ __forceinline__ unsigned int pk4_fp8(float a, float b, float c, float d) {
-    const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    return (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-}
-// eight e4m3 bytes -> the MFMA operand of the 16-bit type (exact: e4m3 values are bf16 / fp16 values)
-__device__ __forceinline__ bf16x8 fp8x8_to_h16(u32x2 w) {
-#if GAR_HALF_F16
-    const h16x2_hw_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[0], 1.0f, false);
-    const h16x2_hw_t b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[0], 1.0f, true);
-    const h16x2_hw_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[1], 1.0f, false);
-    const h16x2_hw_t d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w[1], 1.0f, true);
-#else
-    const bf16x2_hw_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[0], 1.0f, false);
-    const bf16x2_hw_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[0], 1.0f, true);
-    const bf16x2_hw_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[1], 1.0f, false);
-    const bf16x2_hw_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w[1], 1.0f, true);
-#endif
-    const u32x4 r = {__builtin_bit_cast(unsigned int, a), __builtin_bit_cast(unsigned int, b), __builtin_bit_cast(unsigned int, c),
-                     __builtin_bit_cast(unsigned int, d)};
-    return __builtin_bit_cast(bf16x8, r);
-}
-
+// FP8_MAX, pk4_fp8 and fp8x8_to_h16 live in fp8.h (shared with the fp8-weight GEMV of gemm_skinny.hip).
 // ---- gar_kv_quantize_fp8: one wave per (position, kv head, sequence); lanes 0..31 quantize the K vector, 32..63 the V vector
 template <int HD>
 __global__ __launch_bounds__(256) void kv_quantize_fp8_kernel(const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,

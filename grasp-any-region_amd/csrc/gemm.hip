@@ -17,6 +17,7 @@
 bool gar_gemm_pp_try(const gar_gemm_params& p, hipStream_t s);   // gemm_pp.hip
 bool gar_gemm_pp_takes(const gar_gemm_params& p);                // gemm_pp.hip: the predicate alone
 bool gar_skinny_bf16_try(const gar_gemm_params& p, hipStream_t s);   // gemm_skinny.hip
+bool gar_skinny_w8_try(const gar_gemm_params& p, const float* w_scale, hipStream_t s);   // gemm_skinny.hip
 
 // ===============================================================================================================
 // bf16: 128 x 128 x 64
@@ -421,6 +422,41 @@ extern "C" int gar_gemm(int dtype, const gar_gemm_params* pp, gar_stream_t strea
         default: gar_set_error("gar_gemm: unknown epilogue %d", e); return GAR_ERR_ARG;
     }
     if (rc != GAR_OK) return rc;
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
+// The decode GEMV over e4m3 weights (include/gar_hip.h, gar_gemm_w8): `p` as for gar_gemm, with p.W not read.
+extern "C" int gar_gemm_w8(int dtype, const gar_gemm_params* pp, const void* w8, const float* w_scale, gar_stream_t stream) {
+    GAR_CHECK_ARG(pp != nullptr, "gemm_w8: null params");
+    const gar_gemm_params& p = *pp;
+    GAR_CHECK_ARG(dtype == GAR_BF16, "gemm_w8: 16-bit activations only (fp8 weights have no parity mode)");
+    GAR_CHECK_ARG(p.A && w8 && (p.C || p.split_k > 1), "gemm_w8: null operand");
+    GAR_CHECK_ARG(w_scale != nullptr && ((uintptr_t)w_scale & 3) == 0, "gemm_w8: w_scale must be a non-null, 4-byte aligned [N] f32 vector");
+    GAR_CHECK_ARG(p.M > 0 && p.M <= 64 && p.N > 0 && p.K > 0, "gemm_w8: need 0 < M <= 64 (the decode GEMV), N, K > 0 (M=%d N=%d K=%d)",
+                  p.M, p.N, p.K);
+    GAR_CHECK_ARG(p.K % 64 == 0, "gemm_w8: K=%d must be a multiple of 64", p.K);
+    GAR_CHECK_ARG(p.ldw >= p.K && p.ldw % 16 == 0 && ((uintptr_t)w8 & 15) == 0,
+                  "gemm_w8: w8 must be 16-byte aligned with ldw >= K, ldw %% 16 == 0 (bytes)");
+    GAR_CHECK_ARG(((uintptr_t)p.A & 15) == 0 && (p.lda * 2) % 16 == 0, "gemm_w8: A must be 16-byte aligned with 16-byte rows");
+    GAR_CHECK_ARG(!p.row_scale && !p.row_stats, "gemm_w8: row_scale / row_stats belong to the tile GEMM");
+    const int e = p.epilogue;
+    GAR_CHECK_ARG(e == GAR_EPI_NONE || e == GAR_EPI_RES || e == GAR_EPI_SWIGLU,
+                  "gemm_w8: epilogue %d not built (NONE, RES, SWIGLU)", e);
+    if (e == GAR_EPI_RES) GAR_CHECK_ARG(p.residual && p.N % 4 == 0, "gemm_w8: RES needs residual and N %% 4 == 0");
+    if (e == GAR_EPI_SWIGLU) GAR_CHECK_ARG(p.N % 32 == 0, "gemm_w8: SWIGLU needs N %% 32 == 0");
+    if (p.split_k > 1)
+        GAR_CHECK_ARG(e == GAR_EPI_NONE && !p.norm_w && !p.norm_folded && p.partial && p.split_k <= 8 && p.K % (64 * p.split_k) == 0 &&
+                          p.N % 4 == 0,
+                      "gemm_w8: split_k=%d needs GAR_EPI_NONE, no norm, partial, split_k <= 8, K %% (64 split_k) == 0, N %% 4 == 0",
+                      p.split_k);
+    if (p.norm_folded) GAR_CHECK_ARG(!p.norm_w && e != GAR_EPI_RES, "gemm_w8: norm_folded with norm_w or RES");
+    gar_gemm_params q = p;
+    q.W = w8;
+    if (!gar_skinny_w8_try(q, w_scale, (hipStream_t)stream)) {
+        gar_set_error("gemm_w8: no kernel for M=%d epilogue=%d", p.M, e);
+        return GAR_ERR_UNSUPPORTED;
+    }
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }

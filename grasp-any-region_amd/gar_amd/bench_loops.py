@@ -53,6 +53,9 @@ def base_parser(description, default_model, default_cache, default_images):
                          "(gar_amd/continuous.py), so a batch no longer pays for its longest caption in every row")
     ap.add_argument("--kv_cache_dtype", choices=("auto", "fp8"), default="auto",
                     help="decode KV cache: auto = the model dtype; fp8 = OCP e4m3 with one scale per vector (16-bit models only)")
+    ap.add_argument("--decode_weight_dtype", choices=("auto", "fp8"), default="auto",
+                    help="weights of the decode GEMVs: auto = the model dtype; fp8 = OCP e4m3 copies with one scale per output row "
+                         "(16-bit models, decode batches <= 64 rows; the prompt phase keeps 16-bit weights)")
     ap.add_argument("--synthetic_weights", action="store_true")
     return ap
 
@@ -63,6 +66,7 @@ def load(args):
     from .processing import GARProcessor
     dtype = resolve_data_type(args.data_type)
     kv = None if getattr(args, "kv_cache_dtype", "auto") == "auto" else args.kv_cache_dtype
+    dw = None if getattr(args, "decode_weight_dtype", "auto") == "auto" else args.decode_weight_dtype
     rank, local, world = dp.init_distributed()
     device = args.device or f"cuda:{local}"
     torch.cuda.set_device(torch.device(device))
@@ -70,10 +74,10 @@ def load(args):
     if args.synthetic_weights:
         name = args.model_name_or_path if args.model_name_or_path in ("gar_1b", "gar_8b", "tiny") else "gar_1b"
         cfg = getattr(GARConfig, name)()
-        model = GARModel.from_synthetic(cfg, args.seed, dtype, device, kv_cache_dtype=kv)
+        model = GARModel.from_synthetic(cfg, args.seed, dtype, device, kv_cache_dtype=kv, decode_weight_dtype=dw)
         processor = GARProcessor.from_config(cfg, max_num_tiles=args.max_num_tiles)
     else:
-        model = GARModel.from_pretrained(args.model_name_or_path, dtype, device, kv_cache_dtype=kv)
+        model = GARModel.from_pretrained(args.model_name_or_path, dtype, device, kv_cache_dtype=kv, decode_weight_dtype=dw)
         processor = GARProcessor.from_pretrained(args.model_name_or_path, model.config, args.max_num_tiles)
     if not args.host_preprocessing:
         processor.use_gpu_preprocessing(device, dtype)

@@ -57,6 +57,7 @@ class ContinuousBatcher:
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
                  validate: bool = True, use_graph: bool = True, smax_multiple: int = 256):
         self.model, self.B = model, int(slots)
+        model._check_decode_rows(self.B, "ContinuousBatcher slots")
         # every batcher owns its two KV-state slots (decode / staging) of the model: two batchers — or a batcher and a caller of
         # generate(state_slot=...) — on one model never share a cache, token log, eos latches or graph
         base = getattr(model, "_next_batcher_slot", self.FIRST_SLOT)

@@ -71,6 +71,8 @@ SIGNATURES = {
     "gar_attention_decode_fp8": ([_i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
     "gar_attention_decode_qkv_fp8": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp],
                                      _i),
+    "gar_weight_quantize_fp8": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp], _i),
+    "gar_gemm_w8": ([_i, C.POINTER(GemmParams), _vp, _vp, _vp], _i),
     "gar_pool2x2":([_i, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "gar_placeholder_scan": ([_vp, _i, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "gar_pool_assemble": ([_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _vp], _i),

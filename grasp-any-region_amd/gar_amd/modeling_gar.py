@@ -358,7 +358,7 @@ class GARModel:
 
     def __init__(self, config: GARConfig, weights: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16,
                  device: str = "cuda:0", prefill_chunk: Optional[int] = None, keep_plain_weights: bool = False,
-                 kv_cache_dtype: Optional[str] = None):
+                 kv_cache_dtype: Optional[str] = None, decode_weight_dtype: Optional[str] = None):
         self.device = torch.device(device)
         # the decode KV cache: None / "auto" = the model dtype; "fp8" = OCP e4m3fn bytes + one f32 scale per (layer, row, kv head,
         # position), K and V apart (include/gar_hip.h, FP8 KV cache). A property of the model, like its dtype: one model = one
@@ -370,6 +370,18 @@ class GARModel:
             raise hip.GarError(f"kv_cache_dtype='fp8' needs a 16-bit model (bfloat16 / float16), not {dtype}: "
                                "float32 is the parity mode")
         self.kv_cache_dtype = "fp8" if self.kv_fp8 else None
+        # the weights the decode GEMVs stream: None / "auto" = the prepared 16-bit weights; "fp8" = e4m3 copies with one f32 scale
+        # per output row (include/gar_hip.h, FP8 weights) of every Llama layer's qkv / o / gate-up / down operand and of lm_head,
+        # read by decode steps 2 and later. The prompt phase (vision tower, prefill, first token) keeps the 16-bit weights, which
+        # stay resident beside the copies (decode_weight_fp8_bytes). Decode batches above 64 rows run on the tile GEMM: refused.
+        if decode_weight_dtype not in (None, "auto", "fp8"):
+            raise hip.GarError(f"decode_weight_dtype {decode_weight_dtype!r}: None, 'auto' or 'fp8'")
+        self.w_fp8 = decode_weight_dtype == "fp8"
+        if self.w_fp8 and dtype not in HALF_DTYPES:
+            raise hip.GarError(f"decode_weight_dtype='fp8' needs a 16-bit model (bfloat16 / float16), not {dtype}: "
+                               "float32 is the parity mode")
+        self.decode_weight_dtype = "fp8" if self.w_fp8 else None
+        self._w8: Dict[int, tuple] = {}
         # bf16 keeps ONE copy of every weight: the norm-folded forms (ViT qkv / fc1, Llama qkv / gate-up) serve the tile GEMMs
         # (row_scale), the decode GEMVs (norm_folded) and — behind a unit-gain norm pass — the shapes neither takes.
         # keep_plain_weights=True also keeps the un-folded copies (+1.6 GB GAR-1B, +11 GB GAR-8B): A/B switch for FOLD_NORMS = False
@@ -383,6 +395,8 @@ class GARModel:
         with torch.cuda.device(self.device):
             self._prepare_weights(weights)
             self._pack_weights()
+            if self.w_fp8:
+                self._build_w8()
         self.mllm = _MllmFacade(self)
         self.mask_patch_embedding = _MaskPatchEmbedding(self)
         self._mask_only_w = {}
@@ -402,19 +416,20 @@ class GARModel:
 
     @classmethod
     def from_pretrained(cls, path: str, dtype=torch.bfloat16, device="cuda:0", config: GARConfig = None,
-                        kv_cache_dtype: Optional[str] = None):
+                        kv_cache_dtype: Optional[str] = None, decode_weight_dtype: Optional[str] = None):
         import os
         if config is None:
             config = GARConfig.from_json_file(os.path.join(path, "config.json"))
-        return cls(config, normalize_checkpoint(config, load_weights(path)), dtype, device, kv_cache_dtype=kv_cache_dtype)
+        return cls(config, normalize_checkpoint(config, load_weights(path)), dtype, device, kv_cache_dtype=kv_cache_dtype,
+                   decode_weight_dtype=decode_weight_dtype)
 
     @classmethod
-    def from_shapes(cls, config: GARConfig, dtype=torch.bfloat16, device="cuda:0"):
+    def from_shapes(cls, config: GARConfig, dtype=torch.bfloat16, device="cuda:0", **kw):
         """Replica with UNINITIALISED device weights of the right shapes — to be filled by ``broadcast_weights``
         (non-source ranks of the data-parallel runner never touch host weights)."""
         from .weights import weight_shapes
         W = {k: torch.empty(s, dtype=dtype, device=device) for k, s in weight_shapes(config).items()}
-        return cls(config, W, dtype, device)
+        return cls(config, W, dtype, device, **kw)
 
     def _weight_slots(self):
         """where every prepared weight tensor lives: (container, key, index-in-tuple or None), in a fixed order"""
@@ -458,10 +473,48 @@ class GARModel:
         from .dp import broadcast_arenas
         n = broadcast_arenas(self.arenas, src)
         self._mask_only_w.clear()       # derived from w_patch / w_patch_gather (mask_patch_embedding): rebuilt from the new weights
+        if self.w_fp8:                  # derived too: re-quantized in place from the received weights (deterministic: every rank
+            self._build_w8()            # holds the same bytes; captured decode graphs keep their pointers)
         return n
 
     def weight_arena_bytes(self) -> int:
         return sum(a.numel() * a.element_size() for a in self.arenas.values())
+
+    def decode_weight_fp8_bytes(self) -> int:
+        """device bytes of the e4m3 decode-weight copies and their scales (decode_weight_dtype="fp8"; 0 otherwise), held in
+        addition to weight_arena_bytes()"""
+        return sum(q.numel() + 4 * sc.numel() for q, sc in self._w8.values())
+
+    def _build_w8(self):
+        """(Re)build the e4m3 copies the decode GEMVs read: every Llama layer's qkv / o / gate-up / down operand (qkv_f with its
+        permuted rows when folded) and lm_head — a copy when it is tied to E, which embed_lookup keeps reading in 16 bits. Keyed
+        by the 16-bit tensor's data_ptr; an existing copy is rewritten in place."""
+        names = ("qkv_f", "o", "gu_f", "down") if self._decode_uses_folded_w() else ("qkv", "o", "gu", "down")
+        srcs = [ly[k] for ly in self.layers for k in names] + [self.lm_head]
+        old, self._w8 = self._w8, {}
+        for w in srcs:
+            q, sc = old.get(w.data_ptr(), (None, None))
+            self._w8[w.data_ptr()] = ops.weight_quantize_fp8(w, q, sc)
+
+    def _check_decode_rows(self, rows: int, what: str):
+        """decode_weight_dtype="fp8" decodes on the skinny GEMV only: more rows would run on the 16-bit tile GEMM, with other
+        numerics and no notice, so they are refused"""
+        if getattr(self, "w_fp8", False) and rows > self.W8_MAX_ROWS:
+            raise hip.GarError(f"{what}: decode_weight_dtype='fp8' decodes at most {self.W8_MAX_ROWS} rows, not {rows} (larger "
+                               "decode batches run on the 16-bit tile GEMM)")
+
+    def _decode_uses_folded_w(self) -> bool:
+        """the decode step's qkv / gate-up operands: the norm-folded weights (qkv_f / gu_f) or the plain ones (qkv / gu)"""
+        ly = self.layers[0]
+        return "qkv_f" in ly and (self.FOLD_NORMS or "qkv" not in ly)
+
+    def _gemm_w8(self, a, w, out, *args, **kw):
+        """ops.gemm on the e4m3 copy of the prepared 16-bit weight ``w`` (decode steps of a decode_weight_dtype="fp8" model)"""
+        if w.data_ptr() not in self._w8:
+            raise hip.GarError("decode_weight_dtype='fp8': this decode operand has no e4m3 copy (the copies follow FOLD_NORMS as it "
+                               "was at construction)")
+        q, sc = self._w8[w.data_ptr()]
+        return ops.gemm(a, q, out, *args, w_scale=sc, **kw)
 
     def eval(self):
         return self
@@ -616,6 +669,7 @@ class GARModel:
     _CAPACITY_FAMILIES = ("vit", "emb", "prefill")
     MAX_LLM_STATES = 2
     MAX_EOS_IDS = 16          # eos_token_id list entries the device-side stopping criterion holds (longer lists: host scan)
+    W8_MAX_ROWS = 64          # gar_gemm_w8 (decode_weight_dtype="fp8") is the skinny GEMV: M <= 64
     SPLITK_MAX_ROWS = 64      # csrc/gemm.hip: split_k > 1 and gar_splitk_residual_rmsnorm are built for M <= 64 rows
     DOWN_SPLIT_K = 0          # K slices of the decode `down` GEMM at more than FUSE_NORM_MAX_BATCH rows: 0 = as many as give the
                               # two-weight-tile blocks of the skinny kernel a full grid — (hidden / 32) * slices >= 256: 4 at
@@ -1108,9 +1162,11 @@ class GARModel:
         return t
 
     def _head(self, last_rows: torch.Tensor, B: int, out_tokens, st, cur=None, normed: Optional[torch.Tensor] = None,
-              finished=None, row0: int = 0):
+              finished=None, row0: int = 0, decode: bool = False):
         """final RMSNorm + lm_head + greedy argmax of the given [B, C] rows (row-strided view allowed). ``normed``: the
-        rows after the final norm, when the caller's last launch produced them already (split-K decode path)."""
+        rows after the final norm, when the caller's last launch produced them already (split-K decode path). ``decode``: a
+        decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token."""
+        gemm = self._gemm_w8 if decode and self.w_fp8 else ops.gemm
         cur = st["cur"] if cur is None else cur
         t = self.config.mllm_config.text_config
         C_l, V = t.hidden_size, t.vocab_size
@@ -1120,12 +1176,12 @@ class GARModel:
         logits = self._buf(key, "logits", (B, Vld))
         ws = self._buf(key, "amws", (ops.argmax_workspace(B, V),), torch.uint8)
         if normed is not None:
-            ops.gemm(normed, self.lm_head, logits)
+            gemm(normed, self.lm_head, logits)
         elif B <= 16:       # RMSNorm folded into the GEMV prologue; for more rows one tiny norm launch is cheaper
-            ops.gemm(last_rows, self.lm_head, logits, norm_w=self.final_norm, norm_eps=t.rms_norm_eps)
+            gemm(last_rows, self.lm_head, logits, norm_w=self.final_norm, norm_eps=t.rms_norm_eps)
         else:
             ops.rmsnorm(last_rows, self.final_norm, t.rms_norm_eps, out=xn)
-            ops.gemm(xn, self.lm_head, logits)
+            gemm(xn, self.lm_head, logits)
         fin = st["finished"] if finished is None else finished
         if st.get("sampling"):
             ops.sample(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, st["sample_params"], st["sample_seed"],
@@ -1152,8 +1208,9 @@ class GARModel:
         nsplit = max(1, min(self.DECODE_ATTN_MAX_SPLITS, self.DECODE_ATTN_BLOCKS // max(1, B * Hkv)))
         dws = self._buf(key, "attn_ws", (ops.attention_decode_workspace(B, Hq, hd, nsplit),), torch.uint8)
         ops.embed_lookup(st["cur"], self.E, h)
+        gemm = self._gemm_w8 if self.w_fp8 else ops.gemm       # the weight GEMVs: e4m3 copies (decode_weight_dtype="fp8") or 16-bit
         bf16 = self.dtype in HALF_DTYPES
-        use_folded_w = "qkv_f" in self.layers[0] and (self.FOLD_NORMS or "qkv" not in self.layers[0])
+        use_folded_w = self._decode_uses_folded_w()
         # how the two RMSNorms of a layer reach their GEMVs:
         #   folded  (bf16, B <= 64): gain in the weight (qkv_f / gu_f), row sums of squares off the matrix pipe inside the GEMV
         #           (gar_gemm_params.norm_folded) — no norm launch, no normalised copy, ONE copy of the weights
@@ -1177,13 +1234,13 @@ class GARModel:
         xn_ready = False            # xn holds RMSNorm(h; this layer's input_layernorm) — written by the previous layer's reduce
         for li, ly in enumerate(self.layers):
             if qkv_folded:
-                ops.gemm(h, ly["qkv_f"], qkv, norm_folded=True, norm_eps=t.rms_norm_eps)
+                gemm(h, ly["qkv_f"], qkv, norm_folded=True, norm_eps=t.rms_norm_eps)
             elif fuse:
-                ops.gemm(h, ly["qkv"], qkv, norm_w=ly["ln1"], norm_eps=t.rms_norm_eps)
+                gemm(h, ly["qkv"], qkv, norm_w=ly["ln1"], norm_eps=t.rms_norm_eps)
             else:
                 if not xn_ready:
                     ops.rmsnorm(h, self.unit_rms if use_folded_w else ly["ln1"], t.rms_norm_eps, out=xn)
-                ops.gemm(xn, ly["qkv_f"] if use_folded_w else ly["qkv"], qkv)
+                gemm(xn, ly["qkv_f"] if use_folded_w else ly["qkv"], qkv)
             # bf16: RoPE, q scale and the cache append run inside the attention launch (one launch instead of two)
             if self.kv_fp8:     # the fp8 cache has only the fused form: the new row is quantized inside the launch
                 ops.attention_decode_qkv_fp8(qkv, cos, sin, st["Kc"][li], st["Vc"][li], st["Ks"][li], st["Vs"][li], att, B, Hq, Hkv,
@@ -1195,17 +1252,17 @@ class GARModel:
                                  left_pad=st["left_pad"], strip_order=strip)
                 ops.attention_decode(Q, st["Kc"][li], st["Vc"][li], att, B, Hq, Hkv, hd, Smax, kvlen_dev, nsplit, dws,
                                      kv_start=st["left_pad"])
-            ops.gemm(att, ly["o"], h, hip.EPI_RES, residual=h)
+            gemm(att, ly["o"], h, hip.EPI_RES, residual=h)
             if gu_folded:       # W diag(g) + row sums of squares off the matrix pipe: no RMSNorm launch, no normalised copy
-                ops.gemm(h, ly["gu_f"], ff, hip.EPI_SWIGLU, norm_folded=True, norm_eps=t.rms_norm_eps)
+                gemm(h, ly["gu_f"], ff, hip.EPI_SWIGLU, norm_folded=True, norm_eps=t.rms_norm_eps)
             elif fuse:
-                ops.gemm(h, ly["gu"], ff, hip.EPI_SWIGLU, norm_w=ly["ln2"], norm_eps=t.rms_norm_eps)
+                gemm(h, ly["gu"], ff, hip.EPI_SWIGLU, norm_w=ly["ln2"], norm_eps=t.rms_norm_eps)
             else:
                 ops.rmsnorm(h, self.unit_rms if use_folded_w else ly["ln2"], t.rms_norm_eps, out=xn)
-                ops.gemm(xn, ly["gu_f"] if use_folded_w else ly["gu"], ff, hip.EPI_SWIGLU)
+                gemm(xn, ly["gu_f"] if use_folded_w else ly["gu"], ff, hip.EPI_SWIGLU)
             xn_ready = False
             if split > 1:
-                ops.gemm(ff, ly["down"], None, partial=partial)
+                gemm(ff, ly["down"], None, partial=partial)
                 lastl = li + 1 == L
                 # h += down (one rounding, like EPI_RES); the reduce also writes the RMSNorm the next GEMV wants when that GEMV
                 # does not take it folded: the final norm for the head, or the next layer's input_layernorm
@@ -1219,8 +1276,8 @@ class GARModel:
                     ops.splitk_residual_rmsnorm(partial, h, nxt, t.rms_norm_eps, out=xn)
                     xn_ready = True
             else:
-                ops.gemm(ff, ly["down"], h, hip.EPI_RES, residual=h)
-        logits = self._head(h, B, out_tokens, st, normed=normed)
+                gemm(ff, ly["down"], h, hip.EPI_RES, residual=h)
+        logits = self._head(h, B, out_tokens, st, normed=normed, decode=True)
         ops.counter_add(st["counters"][0:3], 1)
         return logits
 
@@ -1312,6 +1369,7 @@ class GARModel:
         max_new_tokens = int(max_new_tokens or 64)
         cfg = self.config
         B, S = input_ids.shape
+        self._check_decode_rows(B, "generate")
         # attention_mask is forwarded to the Llama generate by the reference (modeling_gar.py:418-426). A LEFT-padded batch
         # (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a
         # sequence keeps its rows in the padded layout, its RoPE positions count from its first real token and the padding

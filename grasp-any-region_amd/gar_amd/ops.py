@@ -40,13 +40,20 @@ def _chk(t: torch.Tensor, name: str):
 def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_NONE, bias=None, residual=None,
          gamma=None, pos=None, tokens_in: int = 0, tokens_out: int = 0, token_offset: int = 0, norm_w=None,
          norm_eps: float = 0.0, partial: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None,
-         row_stats: Optional[torch.Tensor] = None, norm_folded: bool = False):
+         row_stats: Optional[torch.Tensor] = None, norm_folded: bool = False, w_scale: Optional[torch.Tensor] = None):
     """out[M, N(/2)] = epilogue(a[M,K] @ w[N,K]^T). `a`, `out`, `residual` may be row-strided 2-D views.
     ``partial`` fp32 [split_k, M, N] (decode GEMMs, EPI_NONE): the K range is cut into split_k slices whose products go
     there instead of ``out`` (pass ``out=None``); ``splitk_residual_rmsnorm`` reduces them.
     ``norm_folded`` (bf16, M <= 64): ``w`` carries an RMSNorm's gain (W diag(g)); the kernel takes rsqrt(mean(a^2) + norm_eps)
-    per row from the tiles of ``a`` it streams and scales the accumulator rows — no norm launch in front of the GEMM."""
+    per row from the tiles of ``a`` it streams and scales the accumulator rows — no norm launch in front of the GEMM.
+    ``w`` uint8 (e4m3 bytes from ``weight_quantize_fp8``) with ``w_scale`` float32 [N]: the fp8-weight decode GEMV
+    (gar_gemm_w8; M <= 64, EPI_NONE / RES / SWIGLU)."""
     assert a.dim() == 2
+    w8 = w.dtype == torch.uint8
+    if w8 != (w_scale is not None):
+        raise hip.GarError("gemm: a uint8 (e4m3) weight goes with its w_scale, and only it")
+    if w8:
+        assert w_scale.dtype == torch.float32 and w_scale.is_contiguous() and w_scale.numel() == w.shape[0], (w_scale.shape, w.shape)
     M, K = a.shape
     p = GemmParams()
     assert w.dim() == 2 and w.shape[1] == K and w.stride(1) == 1, (a.shape, w.shape)
@@ -83,15 +90,41 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epilogue: int = EP
         # HIP events on the launch stream around this one kernel (bench.py roofline; never inside graph capture)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        check(lib(a.dtype).gar_gemm(dtype_code(a.dtype), C.byref(p), stream()), "gar_gemm")
+        _gemm_call(a, p, w, w_scale)
         e1.record()
         # M <= 64: the weight-streaming skinny kernels (decode GEMVs, lm_head, the pruned prefill tail) — HBM-bound, priced on
         # bytes; everything larger is the MFMA-bound tile GEMM family
         kind = ("gemm_skinny" if M <= 64 else "gemm_tile") + ("_f32" if a.dtype == torch.float32 else "_bf16")      # "_bf16": the 16-bit kernels (bf16, or fp16 in the twin library)
-        prof.append((KERNEL_PHASE + kind, 2.0 * M * N * K, (M * K + N * K + M * N) * a.element_size(), e0, e1))
+        nbytes = (M * K + M * N) * a.element_size() + N * K * w.element_size() + (4 * N if w8 else 0)
+        prof.append((KERNEL_PHASE + kind + ("_w8" if w8 else ""), 2.0 * M * N * K, nbytes, e0, e1))
         return out
-    check(lib(a.dtype).gar_gemm(dtype_code(a.dtype), C.byref(p), stream()), "gar_gemm")
+    _gemm_call(a, p, w, w_scale)
     return out
+
+
+def _gemm_call(a, p, w, w_scale):
+    if w_scale is None:
+        check(lib(a.dtype).gar_gemm(dtype_code(a.dtype), C.byref(p), stream()), "gar_gemm")
+    else:
+        check(lib(a.dtype).gar_gemm_w8(dtype_code(a.dtype), C.byref(p), ptr(w), ptr(w_scale), stream()), "gar_gemm_w8")
+
+
+def weight_quantize_fp8(w: torch.Tensor, out: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None):
+    """16-bit ``w`` [N, K] (row-strided view allowed) -> (e4m3 bytes uint8 [N, K], float32 row scales [N]) per
+    include/gar_hip.h: amax = max|row|, inv = 448 / amax, q = e4m3(RNE(w * inv)), scale = amax / 448; rows whose inv is not
+    finite are zeros with scale 0. ``out`` / ``scale`` are written in place when given (a rebuild keeps the pointers)."""
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    if scale is None:
+        scale = torch.empty((N,), dtype=torch.float32, device=w.device)
+    assert out.dtype == torch.uint8 and out.shape == (N, K) and out.stride(1) == 1
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == N
+    _timed("weight_quantize_fp8", N * K * (2 * w.element_size() + 1) + 4 * N, lambda: check(
+        lib(w.dtype).gar_weight_quantize_fp8(dtype_code(w.dtype), ptr(w), int(w.stride(0)), N, K, ptr(out), int(out.stride(0)),
+                                             ptr(scale), stream()), "gar_weight_quantize_fp8"))
+    return out, scale
 
 
 def tile_gemm_takes(M: int, N: int, K: int = 64, lda: int = 0, ldc: int = 0, ldr: int = 0, epilogue: int = EPI_NONE,

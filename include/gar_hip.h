@@ -300,6 +300,25 @@ int gar_attention_decode_qkv_fp8(int dtype, const void* qkv, const float* cos, c
                                  const int32_t* left_pad, float q_scale, int qk_strip_order, int max_splits, void* workspace,
                                  gar_stream_t stream);
 
+/* ---- FP8 weights for the decode GEMVs (GARModel(decode_weight_dtype="fp8")) ------------------------------------------------
+ * Additive: two new entry points, gar_gemm_params unchanged, so GAR_ABI_VERSION stays 16.
+ * A weight W [N, K] 16-bit is stored as OCP e4m3fn bytes W8 [N, K] (row stride ldq bytes) and one f32 scale per ROW, in the
+ * KV cache's operations: amax = max_k |W[n][k]|, inv = 448 / amax, W8[n][k] = e4m3(RNE(W[n][k] * inv)), scale[n] = amax / 448;
+ * a row whose inv is not finite is stored as zeros with scale 0. (w.float() * inv).to(torch.float8_e4m3fn) restates it byte
+ * for byte. 16-bit types only (dtype GAR_BF16 — bf16, or fp16 in the twin library).
+ *
+ * gar_weight_quantize_fp8: W [N, K] (row stride ldw elements, K % 8 == 0) -> W8, scale [N]. One block per row; one-off at load. */
+int gar_weight_quantize_fp8(int dtype, const void* W, int64_t ldw, int N, int K, void* W8, int64_t ldq, float* scale,
+                            gar_stream_t stream);
+/* gar_gemm over e4m3 weights, the skinny decode GEMV of gar_gemm at M <= 64 with the weight tiles streamed as bytes:
+ *     C[m][n] = epilogue(rstd_m * w_scale[n] * sum_k A[m][k] * W8[n][k])
+ * The dot product is the 16-bit MFMA on the exact 16-bit images of the bytes with f32 accumulation; w_scale[n] multiplies the
+ * f32 accumulator before the residual add, the SwiGLU and the split-K partial store; rstd_m only with norm_w / norm_folded.
+ * `p` as for gar_gemm (p.W is not read; p.ldw = row stride of w8 in bytes): M <= 64, K % 64 == 0, GAR_EPI_NONE / RES / SWIGLU,
+ * norm_w, norm_folded and split_k as gar_gemm takes them on the decode GEMVs, no row_scale / row_stats. w8 16-byte aligned,
+ * ldw % 16 == 0; w_scale [N] f32, non-null. */
+int gar_gemm_w8(int dtype, const gar_gemm_params* p, const void* w8, const float* w_scale, gar_stream_t stream);
+
 /* PerceptionLMAdaptiveAvgPooling (modeling_perception_lm.py:47-60): per tile [g*g, C] -> [(g/2)^2, C], exact 2x2
  * mean. Input tile t starts at row t*in_tile_tokens + in_token_offset of x (lets the projector run over the
  * cls-inclusive token matrix and drop the cls row here, modeling_perception_lm.py:263-264). */
