@@ -140,6 +140,14 @@ struct gar_gather_args {
 };
 #define GATHER_KT_PER_TENSOR 12     // 3 channels x 4 K tiles (16 ky slots)
 
+// Fused lm_head + cross-entropy (gar_lm_head_xent): an instantiation of this kernel whose epilogue never stores the [M, N]
+// product. It is no public GAR_EPI_* value: gar_gemm does not take it. Its extra operands ride in fields the other epilogues
+// name but this one does not read: p.pos = int32 targets [M] (any value; only a column in [0, N) is ever matched),
+// p.C = float2 partials [M][p.ldc] with p.ldc = 4 * ceil(N / 256) (one per row and 64-column wave strip: (max, sum exp(x - max))
+// of the strip's logits x, each rounded to the 16-bit type first; a strip wholly past N holds (-inf, 0)), p.residual = f32 [M]
+// target logit (written by the one lane whose strip holds the target column; left alone when no column matches).
+#define PP_EPI_XENT 64
+
 template <int EPI, bool GATHER = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const gar_gemm_params p, int tiles_m, int tiles_n,
                                                               const gar_gather_args ga) {
@@ -368,6 +376,51 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const gar_gemm_par
             for (int i = 0; i < 8; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
+            return;
+        }
+        if (EPI == PP_EPI_XENT) {
+            // lane (frow, fq) holds, for each of its 8 rows i, columns 32 (j >> 1) + 8 fq + 4 (j & 1) + r of the wave's 64-column
+            // strip; the strip's four fq lanes of a row are lanes frow + 16 fq: max and sum over them by two xor shuffles
+            const int nw0 = n0 + wn * 64;
+            const int strip = (n0 >> 6) + wn;
+            float2* const part = (float2*)p.C;
+            const int32_t* const tgt = (const int32_t*)p.pos;
+            float* const tl = (float*)p.residual;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int m = m0 + wm * 128 + i * 16 + frow;
+                float x[16];
+                float mx = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int c = 32 * (j >> 1) + 8 * fq + 4 * (j & 1) + r;
+                        const float v = bf2f(f2bf(acc[i][j][r]));          // the logit as the model dtype holds it
+                        x[j * 4 + r] = nw0 + c < p.N ? v : -INFINITY;
+                        mx = fmaxf(mx, x[j * 4 + r]);
+                    }
+                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                float se = 0.f;
+                if (mx != -INFINITY) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) se += __builtin_amdgcn_exp2f((x[e] - mx) * 1.4426950408889634f);
+                }
+                se += __shfl_xor(se, 16, 64);
+                se += __shfl_xor(se, 32, 64);
+                if (m < p.M) {
+                    if ((i & 3) == fq) part[(int64_t)m * p.ldc + strip] = make_float2(mx, se);
+                    const int c = tgt[m] - nw0;        // the target column inside this strip, if it is there
+                    if (c >= 0 && c < 64 && ((c & 31) >> 3) == fq && nw0 + c < p.N) {
+                        const int sel = (c >> 5) * 8 + ((c >> 2) & 1) * 4 + (c & 3);      // = 4 j + r
+                        float v = 0.f;
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) v = e == sel ? x[e] : v;
+                        tl[m] = v;
+                    }
+                }
+            }
             return;
         }
         if (EPI == GAR_EPI_SWIGLU) {
@@ -775,12 +828,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const gar_gemm_par
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[i][j][r] = __builtin_fmaf(acc[i][j][r], rs[i], bv[j][r]);
         }
-        constexpr bool WAVE_EPI = EPI != GAR_EPI_SWIGLU;
+        constexpr bool WAVE_EPI = EPI != GAR_EPI_SWIGLU && EPI != PP_EPI_XENT;
         if (PERM && LDS_EPI && WAVE_EPI && !PP_DIAG_NOSTORE && (EPI != GAR_EPI_QKV_ROPE || (p.qkv_cos == nullptr && p.qkv_v != nullptr))) {
             epilogue_wave(smem + (sidx ^ 1) * PSTAGE);      // starts at once in each wave row; un-staggers inside
         } else {
             if (wm == 0) __builtin_amdgcn_s_barrier();
-            if (PERM && LDS_EPI && !PP_DIAG_NOSTORE) epilogue_lds(smem + (sidx ^ 1) * PSTAGE);
+            if (PERM && LDS_EPI && !PP_DIAG_NOSTORE && EPI != PP_EPI_XENT) epilogue_lds(smem + (sidx ^ 1) * PSTAGE);
             else epilogue();
         }
 #if PP_TIMELINE == 4
@@ -901,6 +954,46 @@ bool gar_gemm_pp_takes(const gar_gemm_params& p) {
         return false;
     if (p.row_stats && !(e_ == GAR_EPI_RES || e_ == GAR_EPI_BIAS_SCALE_RES)) return false;
     return e_ >= GAR_EPI_NONE && e_ <= GAR_EPI_QKV_ROPE_LLM;
+}
+
+// ---- fused lm_head + cross-entropy (include/gar_hip.h, gar_lm_head_xent) ------------------------------------------------
+static bool xent_takes(int dtype, int R, int V, int C, int64_t lda, int64_t ldw) {
+    return dtype == GAR_BF16 && R > 64 && V > 0 && C > 0 && C % 64 == 0 && lda % 8 == 0 && ldw % 8 == 0 && lda >= C &&
+           ldw >= C && ((int64_t)(R - 1) * lda + C) * 2 < ((int64_t)1 << 32) - 4096 &&
+           ((int64_t)(V - 1) * ldw + C) * 2 < ((int64_t)1 << 32) - 4096;
+}
+
+extern "C" int gar_lm_head_xent_takes(int dtype, int R, int V, int C) { return xent_takes(dtype, R, V, C, C, C) ? 1 : 0; }
+
+extern "C" int gar_lm_head_xent_strips(int V) { return V > 0 ? 4 * ((V + PBM - 1) / PBM) : 0; }
+
+extern "C" int gar_lm_head_xent(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, int R, int V, int C,
+                                const int32_t* targets, float* partials, float* target_logit, gar_stream_t stream) {
+    GAR_CHECK_ARG(A && W && targets && partials && target_logit, "lm_head_xent: null pointer");
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    GAR_CHECK_ARG(al16(A) && al16(W) && ((uintptr_t)partials & 7) == 0, "lm_head_xent: A / W must be 16-byte aligned");
+    if (!xent_takes(dtype, R, V, C, lda, ldw)) {
+        gar_set_error("lm_head_xent: built for the 16-bit tile GEMM, R > 64 rows, C %% 64 == 0, operands < 4 GiB "
+                      "(dtype=%d R=%d V=%d C=%d)", dtype, R, V, C);
+        return GAR_ERR_UNSUPPORTED;
+    }
+    gar_gemm_params p = {};
+    p.A = A;
+    p.lda = lda;
+    p.W = W;
+    p.ldw = ldw;
+    p.M = R;
+    p.N = V;
+    p.K = C;
+    p.epilogue = PP_EPI_XENT;
+    p.C = partials;
+    p.ldc = gar_lm_head_xent_strips(V);
+    p.pos = targets;
+    p.residual = target_logit;
+    const int pm = (R + PBM - 1) / PBM, pn = (V + PBM - 1) / PBM;
+    launch_pp<PP_EPI_XENT>(p, pm, pn, pp_num_cus(), (hipStream_t)stream);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
 }
 
 // returns true if the problem was taken

@@ -355,6 +355,62 @@ extern "C" int gar_rmsnorm(int dtype, const void* x, void* y, const void* w, int
     return launch_norm<true>(dtype, x, y, w, nullptr, M, D, ldx, ldy, eps, stream);
 }
 
+// Gather + RMSNorm (gar_gather_rmsnorm, caption scoring): y[r, :] = LlamaRMSNorm(x[rows[r], :]; w), one wave per gathered row,
+// the arithmetic of norm_kernel<T, true, ...> in the same order (per-lane fma chain over the row's 512-element chunks, then
+// wave_sum, rsqrtf, rms_out): the result equals gar_rmsnorm on the gathered rows bit for bit. A row index outside [0, M)
+// gives a row of zeros.
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rms_kernel(const T* __restrict__ x, int64_t ldx, int M, const int32_t* __restrict__ rows,
+                                                         int R, const T* __restrict__ w, T* __restrict__ y, int D, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const int src = rows[r];
+    T* yr = y + (int64_t)r * D;
+    if (src < 0 || src >= M) {
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int i = lane * 8; i < D; i += 512) st8(yr + i, z);
+        return;
+    }
+    const T* xr = x + (int64_t)src * ldx;
+    float s = 0.f;
+    for (int i = lane * 8; i < D; i += 512) {
+        float t[8];
+        ld8(xr + i, t);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s = __fmaf_rn(t[e], t[e], s);
+    }
+    s = wave_sum(s);
+    const float rstd = rsqrtf(s / (float)D + eps);
+    for (int i = lane * 8; i < D; i += 512) {
+        float t[8], ww[8], o[8];
+        ld8(xr + i, t);
+        ld8(w + i, ww);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = rms_out<T>(t[e], rstd, ww[e]);
+        st8(yr + i, o);
+    }
+}
+
+extern "C" int gar_gather_rmsnorm(int dtype, const void* x, int64_t ldx, int M, const int32_t* rows, int R, const void* w,
+                                  void* y, int D, float eps, gar_stream_t stream) {
+    GAR_CHECK_ARG(dtype == GAR_F32 || dtype == GAR_BF16, "gather_rmsnorm: bad dtype");
+    GAR_CHECK_ARG(x && rows && w && y, "gather_rmsnorm: null pointer");
+    GAR_CHECK_ARG(M > 0 && R > 0 && D > 0 && D % 8 == 0, "gather_rmsnorm: bad shape (M %d, R %d, D %d: D %% 8 == 0)", M, R, D);
+    if (ldx <= 0) ldx = D;
+    GAR_CHECK_ARG(ldx % 8 == 0, "gather_rmsnorm: row stride must be a multiple of 8 elements");
+    dim3 grid((R + 3) / 4), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((gather_rms_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)x, ldx, M, rows, R, (const bf16_t*)w,
+                           (bf16_t*)y, D, eps);
+    else
+        hipLaunchKernelGGL((gather_rms_kernel<float>), grid, block, 0, s, (const float*)x, ldx, M, rows, R, (const float*)w,
+                           (float*)y, D, eps);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Statistics half of a norm folded into the GEMM pair around it (gar_gemm_params.row_scale / row_stats, ABI v8).
 // row_rstd_kernel: one wave per row straight from x (two-pass variance like norm_kernel) — the first norm of a chain.

@@ -90,6 +90,11 @@ SIGNATURES = {
     "gar_sample": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp], _i),
     "gar_counter_add": ([_vp, _i, _i, _vp], _i),
     "gar_input_check": ([_vp, _i, _i, _i64, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "gar_gather_rmsnorm": ([_i, _vp, _i64, _i, _vp, _i, _vp, _vp, _i, _f, _vp], _i),
+    "gar_lm_head_xent_takes": ([_i, _i, _i, _i], _i),
+    "gar_lm_head_xent_strips": ([_i], _i),
+    "gar_lm_head_xent": ([_i, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "gar_xent_combine": ([_i, _vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
 }
 
 _lib = None

@@ -51,6 +51,7 @@ class GenerateOutput:
 
 
 INPUT_COUNT_MISMATCH, INPUT_SPAN_LENGTH, INPUT_MISSING_BBOX, INPUT_ID_RANGE, INPUT_MASK_NOT_LEFT_PADDED = 1, 2, 4, 8, 16
+INPUT_LABEL_RANGE = 32          # score(validate=False): a label outside [0, vocab) and not -100 (set by gar_xent_combine)
 
 
 def describe_input_flags(flags: int) -> str:
@@ -59,8 +60,48 @@ def describe_input_flags(flags: int) -> str:
              INPUT_MISSING_BBOX: "a crop token present in input_ids has no bbox (reference: KeyError)",
              INPUT_ID_RANGE: "input_ids outside [0, vocab)",
              INPUT_MASK_NOT_LEFT_PADDED: "attention_mask is not LEFT-padded (a row is not 0...01...1): HF generation would continue "
-                                         "such a row after its padding"}
+                                         "such a row after its padding",
+             INPUT_LABEL_RANGE: "labels outside [0, vocab) other than -100 (ignored; validate=True raises ValueError)"}
     return "; ".join(v for k, v in names.items() if flags & k)
+
+
+@dataclass
+class ScoreOutput:
+    """:meth:`GARModel.score`: teacher-forced log-probabilities, all on the device."""
+    token_logprobs: torch.Tensor                 # f32 [B, S]: log p(labels[t] | prefix) at column t; 0 where ignored
+    sum_logprobs: torch.Tensor                   # f32 [B]
+    n_tokens: torch.Tensor                       # int32 [B]: scored tokens per row
+    loss: torch.Tensor                           # f32 0-dim: -sum / count over the batch (HF's mean; NaN with no token)
+    input_flags: Optional[torch.Tensor] = None   # validate=False only: int32 [1], INPUT_* bits (INPUT_LABEL_RANGE included)
+
+
+def score_targets(input_ids: torch.Tensor, labels: torch.Tensor, crop_ids: Sequence[int],
+                  attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The label semantics of the reference's loss (modeling_gar.py:176-190 + HF's causal-LM shift), in torch ops on the
+    labels' device, no host sync: int64 [B, S - 1], entry t = the target of row t (its next token), -100 where ignored.
+    Inside each crop token's span (first to last occurrence), which the RoI replay replaces, labels become -100. With a
+    left-padding ``attention_mask``, a padding row predicts nothing, so the first real token is not scored (as in the
+    unpadded run)."""
+    ids = input_ids.to(labels.device, torch.int64)
+    lab = labels.to(torch.int64).clone()
+    B, S = ids.shape
+    col = torch.arange(S, device=lab.device)[None, :]
+    for c in crop_ids:
+        hit = ids == int(c)
+        first = torch.where(hit, col, S).min(1).values[:, None]
+        last = torch.where(hit, col, -1).max(1).values[:, None]
+        lab = lab.masked_fill((col >= first) & (col <= last), -100)
+    tgt = lab[:, 1:]
+    if attention_mask is not None:
+        tgt = tgt.masked_fill(~(attention_mask.to(lab.device) != 0)[:, :-1], -100)
+    return tgt
+
+
+def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """HF's ForCausalLMLoss restated: logits cast to f32, labels shifted by one, cross-entropy with ignore_index=-100, mean
+    over the tokens that remain (NaN with none)."""
+    lg = logits.float()[:, :-1].reshape(-1, logits.shape[-1])
+    return torch.nn.functional.cross_entropy(lg, labels[:, 1:].reshape(-1).to(lg.device), ignore_index=-100, reduction="mean")
 
 
 # GenerationConfig fields the reference forwards to HF's generate (modeling_gar.py:418-426) that would change the tokens of a
@@ -666,7 +707,7 @@ class GARModel:
     # with a different prompt length / tile count per item (gar_amd/bench_loops.py) does not allocate per shape.
     # Buffers a captured decode graph points at ("llm", "decode", "head") are keyed by their exact shape and never move;
     # the KV-cache states are kept in an LRU of MAX_LLM_STATES entries (their graphs go with them).
-    _CAPACITY_FAMILIES = ("vit", "emb", "prefill")
+    _CAPACITY_FAMILIES = ("vit", "emb", "prefill", "score")
     MAX_LLM_STATES = 2
     MAX_EOS_IDS = 16          # eos_token_id list entries the device-side stopping criterion holds (longer lists: host scan)
     W8_MAX_ROWS = 64          # gar_gemm_w8 (decode_weight_dtype="fp8") is the skinny GEMV: M <= 64
@@ -1020,9 +1061,11 @@ class GARModel:
             st["Vs"] = self._buf(key, "Vs", (L, B, Hkv, Smax), torch.float32, zero=True)
         return key, st
 
-    def _prefill(self, embeds: torch.Tensor, st, Smax: int, b0: int = 0):
+    def _prefill(self, embeds: torch.Tensor, st, Smax: int, b0: int = 0, prune: Optional[bool] = None):
         """Prefill of one chunk of sequences [B,S,C] whose KV goes to rows b0..b0+B of the shared cache. Returns the last
-        prompt row of every sequence after the last layer ([B, C] row-strided view): what the head reads."""
+        prompt row of every sequence after the last layer ([B, C] row-strided view): what the head reads. ``prune``: None =
+        PRUNE_LAST_PREFILL_LAYER; False runs the last layer at full width, so every row of ``embeds`` holds the residual
+        stream after the last layer (what :meth:`score` reads)."""
         t = self.config.mllm_config.text_config
         B, S, C_l = embeds.shape
         Hq, Hkv, hd, F = t.num_attention_heads, t.num_key_value_heads, t.head_dim, t.intermediate_size
@@ -1055,7 +1098,7 @@ class GARModel:
         fused_qkv = fold and self.LLM_QKV_EPILOGUE and hd in (64, 128)
         strip = use_folded_w and self.qkv_f_permuted        # q / k head columns of a qkv_f product are in the fused epilogue's order
         L = len(self.layers)
-        prune = self.PRUNE_LAST_PREFILL_LAYER and S > 1
+        prune = (self.PRUNE_LAST_PREFILL_LAYER if prune is None else prune) and S > 1
         att = ff = None
         if L > 1 or not prune:
             att = self._buf(key, "att", (M, Hq * hd))
@@ -1306,6 +1349,75 @@ class GARModel:
         seq_chunks = plan_chunks(B, S, llm_gemms, lrows, cus)
         return tile_chunks, seq_chunks
 
+    def _left_pad(self, attention_mask, B: int, S: int, validate: bool):
+        """(left_pad int32 [B] or None, the mask on the device when validate=False or None) of a LEFT-padded attention_mask."""
+        left_pad = am_dev = None
+        if attention_mask is not None:
+            am = (attention_mask != 0)
+            if tuple(am.shape) != (B, S):
+                raise ValueError(f"attention_mask {tuple(am.shape)} does not match input_ids {(B, S)}")
+            if validate:
+                amc = am.cpu()
+                if not bool(amc.all()):
+                    if not bool((amc[:, 1:] >= amc[:, :-1]).all()) or not bool(amc[:, -1].all()):
+                        raise hip.GarError("attention_mask must be LEFT-padded (zeros only in front of every prompt): a "
+                                           "right-padded row would be continued after its padding")
+                    left_pad = (S - amc.sum(1)).to(torch.int32).to(self.device)
+            else:                      # no host sync: the zero count is the pad; the device-side input check (gar_input_check)
+                am_dev = am.to(self.device).contiguous()       # raises INPUT_MASK_NOT_LEFT_PADDED for a row that is not 0...01...1
+                left_pad = (S - am_dev.sum(1)).to(torch.int32)
+        return left_pad, am_dev
+
+    def _prompt_chunks(self, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate: bool,
+                       feature_replay_video: bool = False, video_frame_tokens: Optional[Sequence[int]] = None):
+        """The prompt phase up to the prefill, shared by generate_begin and score: the vision tower over chunks of image tiles,
+        then per chunk of sequences the assembled and RoI-replayed embeddings. Yields (b0, b1, embeds [b1 - b0, S, C]); the
+        caller prefills each chunk before it asks for the next (the embeddings buffer is reused)."""
+        cfg = self.config
+        B, S = input_ids.shape
+        C_l = cfg.mllm_config.text_config.hidden_size
+        tiles = 0
+        if pixel_values is not None:
+            tiles = pixel_values.shape[0] // B if pixel_values.dim() == 4 else pixel_values.shape[1]
+            pv = pixel_values.reshape(B, tiles, *pixel_values.shape[-3:])
+            gm = None if global_mask_values is None else global_mask_values.reshape(pv.shape)
+            if feature_replay_video and video_frame_tokens is None:
+                # <|reserved_special_token_{2+f}|> of frame f (modeling_perception_lm.py:777-780): the first
+                # prompt_numbers ids are config.crop_tokens_ids, the following reserved tokens are consecutive ids
+                base = list(self.crop_tokens_ids)
+                video_frame_tokens = (base + [base[-1] + 1 + i for i in range(max(0, tiles - len(base)))])[:tiles]
+        # The vision tower runs over chunks of image tiles and the prefill over chunks of sequences (bounded activation
+        # memory, GEMM operands < 4 GiB; sizes from _plan_passes); the projector output of the whole batch is kept, and
+        # the decode loop then serves all B sequences of the shared KV cache in one weight pass per token.
+        tile_chunks, seq_chunks = self._plan_passes(B, tiles, S)
+        proj_all, rows_per_sample = None, 0
+        if pixel_values is not None:
+            v = cfg.mllm_config.vision_config
+            rows_per_sample = tiles * (v.num_patches + self.npt)
+            proj_all = self._buf(("vit", "all"), "proj_all", (B * rows_per_sample, C_l))
+            pvf = pv.reshape(B * tiles, *pv.shape[-3:])
+            gmf = None if gm is None else gm.reshape(pvf.shape)
+            t0 = 0
+            for tc in tile_chunks:
+                r0, r1 = t0 * (v.num_patches + self.npt), (t0 + tc) * (v.num_patches + self.npt)
+                self.get_image_features(pvf[t0:t0 + tc], None if gmf is None else gmf[t0:t0 + tc], pooled=False,
+                                        out=proj_all[r0:r1])
+                t0 += tc
+        b0 = 0
+        for sc in seq_chunks:
+            b1 = b0 + sc
+            ids_c = input_ids[b0:b1]
+            if pixel_values is not None:
+                ar_c = None if aspect_ratios is None else aspect_ratios[b0:b1]
+                embeds = self.build_inputs_embeds(ids_c, None, bboxes[b0:b1], ar_c, tiles, validate,
+                                                  video_frame_tokens if feature_replay_video else None,
+                                                  proj=proj_all[b0 * rows_per_sample:b1 * rows_per_sample])
+            else:
+                embeds = self._buf(("emb", b1 - b0, S), "embeds", (b1 - b0, S, C_l))
+                ops.embed_assemble(ids_c.to(self.device, torch.int64).contiguous(), None, self.E, None, embeds, 0)
+            yield b0, b1, embeds
+            b0 = b1
+
     # ---- generate -------------------------------------------------------------------------------------------------
     def generate(self, *args, **kwargs) -> GenerateOutput:
         """Greedy region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): the prompt phase
@@ -1374,21 +1486,7 @@ class GARModel:
         # (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a
         # sequence keeps its rows in the padded layout, its RoPE positions count from its first real token and the padding
         # keys stay hidden (HF: position_ids = cumsum(mask) - 1, causal mask AND attention_mask).
-        left_pad = am_dev = None
-        if attention_mask is not None:
-            am = (attention_mask != 0)
-            if tuple(am.shape) != (B, S):
-                raise ValueError(f"attention_mask {tuple(am.shape)} does not match input_ids {(B, S)}")
-            if validate:
-                amc = am.cpu()
-                if not bool(amc.all()):
-                    if not bool((amc[:, 1:] >= amc[:, :-1]).all()) or not bool(amc[:, -1].all()):
-                        raise hip.GarError("attention_mask must be LEFT-padded (zeros only in front of every prompt): a "
-                                           "right-padded row would be continued after its padding")
-                    left_pad = (S - amc.sum(1)).to(torch.int32).to(self.device)
-            else:                      # no host sync: the zero count is the pad; the device-side input check (gar_input_check)
-                am_dev = am.to(self.device).contiguous()       # raises INPUT_MASK_NOT_LEFT_PADDED for a row that is not 0...01...1
-                left_pad = (S - am_dev.sum(1)).to(torch.int32)
+        left_pad, am_dev = self._left_pad(attention_mask, B, S, validate)
         # KV capacity in buckets of 256 positions: evaluation loops with a different prompt length per item reuse one
         # cache, one token buffer ([B, Smax], sliced) and one captured decode graph per bucket
         if forced_tokens is not None:
@@ -1422,58 +1520,19 @@ class GARModel:
             st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0], torch.float32))
             st["sample_seed"].copy_(self._upload([int(seed)], torch.int64, cache=False))
         V = cfg.mllm_config.text_config.vocab_size
-        tiles = 0
-        if pixel_values is not None:
-            tiles = pixel_values.shape[0] // B if pixel_values.dim() == 4 else pixel_values.shape[1]
-            pv = pixel_values.reshape(B, tiles, *pixel_values.shape[-3:])
-            gm = None if global_mask_values is None else global_mask_values.reshape(pv.shape)
-            if feature_replay_video and video_frame_tokens is None:
-                # <|reserved_special_token_{2+f}|> of frame f (modeling_perception_lm.py:777-780): the first
-                # prompt_numbers ids are config.crop_tokens_ids, the following reserved tokens are consecutive ids
-                base = list(self.crop_tokens_ids)
-                video_frame_tokens = (base + [base[-1] + 1 + i for i in range(max(0, tiles - len(base)))])[:tiles]
-        # The vision tower runs over chunks of image tiles and the prefill over chunks of sequences (bounded activation
-        # memory, GEMM operands < 4 GiB; sizes from _plan_passes); the projector output of the whole batch is kept, and
-        # the decode loop below then serves all B sequences of the shared KV cache in one weight pass per token.
         first_logits = []
         self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
         if am_dev is not None:      # validate=False: the mask's left-padded form is checked on the device, flag read by the caller
             ops.input_check(input_ids.to(self.device, torch.int64).contiguous(), V, None, 0, None, 0, None, self._input_flags,
                             attn_mask=am_dev)
-        tile_chunks, seq_chunks = self._plan_passes(B, tiles, S)
-        proj_all, rows_per_sample = None, 0
-        if pixel_values is not None:
-            v = cfg.mllm_config.vision_config
-            C_l = cfg.mllm_config.text_config.hidden_size
-            rows_per_sample = tiles * (v.num_patches + self.npt)
-            proj_all = self._buf(("vit", "all"), "proj_all", (B * rows_per_sample, C_l))
-            pvf = pv.reshape(B * tiles, *pv.shape[-3:])
-            gmf = None if gm is None else gm.reshape(pvf.shape)
-            t0 = 0
-            for tc in tile_chunks:
-                r0, r1 = t0 * (v.num_patches + self.npt), (t0 + tc) * (v.num_patches + self.npt)
-                self.get_image_features(pvf[t0:t0 + tc], None if gmf is None else gmf[t0:t0 + tc], pooled=False,
-                                        out=proj_all[r0:r1])
-                t0 += tc
-        b0 = 0
-        for sc in seq_chunks:
-            b1 = b0 + sc
-            ids_c = input_ids[b0:b1]
-            if pixel_values is not None:
-                ar_c = None if aspect_ratios is None else aspect_ratios[b0:b1]
-                embeds = self.build_inputs_embeds(ids_c, None, bboxes[b0:b1], ar_c, tiles, validate,
-                                                  video_frame_tokens if feature_replay_video else None,
-                                                  proj=proj_all[b0 * rows_per_sample:b1 * rows_per_sample])
-            else:
-                embeds = self._buf(("emb", b1 - b0, S), "embeds", (b1 - b0, S, cfg.mllm_config.text_config.hidden_size))
-                ops.embed_assemble(ids_c.to(self.device, torch.int64).contiguous(), None, self.E, None, embeds, 0)
+        for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
+                                                  feature_replay_video, video_frame_tokens):
             last = self._prefill(embeds, st, Smax, b0)
             lg = self._head(last, b1 - b0, out_tokens[b0:b1], st, cur=st["cur"][b0:b1], finished=st["finished"][b0:b1], row0=b0)
             if forced_tokens is not None:
                 st["cur"][b0:b1].copy_(forced_tokens[b0:b1, 0])
             if return_logits:
                 first_logits.append(lg[:, :V].float().clone())
-            b0 = b1
         all_logits = []
         if return_logits:
             all_logits.append(torch.cat(first_logits, 0))
@@ -1489,6 +1548,123 @@ class GARModel:
                                   eos=eos, eos_first=eos_first, pad_token_id=pad_token_id, return_logits=return_logits,
                                   all_logits=all_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
                                   sync_every=sync_every, input_flags=self._input_flags)
+
+    # ---- teacher-forced scoring ---------------------------------------------------------------------------------------
+    XENT_CHUNK_ROWS = 8192          # scored rows per fused-head launch: partials workspace <= chunk x 16 KiB at V = 128256
+    XENT_DENSE_ROWS = 64            # rows per launch of the dense form (skinny GEMM to [rows, V] logits + combine)
+
+    def forward(self, data, data_samples=None, mode: str = "loss"):
+        """The reference's training entry point (modeling_gar.py:74-246) in its ``mode="loss"`` form: ``{"loss": tensor}``, HF's
+        causal-LM loss of ``data["labels"]`` with labels inside every replayed crop-token span set to -100, positions 0..S-1 and
+        an all-ones attention mask. ``data`` holds pixel_values, global_mask_values, input_ids, aspect_ratios, bboxes, labels.
+        B >= 1 (the reference asserts 1): the mean over all valid tokens of the batch, as HF computes it. No gradients."""
+        if mode != "loss":
+            raise hip.GarError(f"forward(mode={mode!r}): only mode='loss' is built (the reference's 'predict' / 'tensor' "
+                               "modes return an undefined value)")
+        out = self.score(data["pixel_values"], data["global_mask_values"], data["aspect_ratios"], data["bboxes"],
+                         data["input_ids"], data["labels"])
+        return {"loss": out.loss}
+
+    __call__ = forward
+
+    @_on_model_device
+    @torch.no_grad()
+    def score(self, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, labels, attention_mask=None,
+              validate: bool = True, state_slot: int = 0) -> ScoreOutput:
+        """Teacher-forced log-probabilities of ``labels`` [B, S] (-100 = ignored) under the prompt ``input_ids`` [B, S]: the
+        batched form under :meth:`forward`. Column t + 1 of ``token_logprobs`` holds log p(labels[t + 1] | rows 0..t), f32, 0
+        where ignored (labels -100, the replayed crop-token spans, padding). Arguments as :meth:`generate_begin`; a LEFT-padded
+        ``attention_mask`` follows generate's rules (RoPE positions from each row's first real token, padding keys hidden).
+
+        The prompt phase of generate (vision tower, sequence assembly + RoI replay, prefill) with the last layer at full width,
+        then one gather + final-RMSNorm launch over the scored rows and the lm_head fused with the cross-entropy (the tile GEMM
+        writes per-strip (max, sum exp) partials, never the [rows, V] logits); below 65 rows, or in f32, 64-row chunks of
+        dense logits. Models built with kv_cache_dtype="fp8" or decode_weight_dtype="fp8" score with 16-bit numerics: the
+        prompt phase uses neither option.
+
+        ``validate=False``: no host sync. Labels are not checked on the host (one outside [0, vocab) other than -100 is
+        ignored and sets INPUT_LABEL_RANGE in ``input_flags``), the input checks of generate(validate=False) go to the same
+        flag, and the head runs over every row, since the number of labelled rows is not known without a sync."""
+        cfg = self.config
+        t = cfg.mllm_config.text_config
+        V, C_l = t.vocab_size, t.hidden_size
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, S], got {tuple(input_ids.shape)}")
+        B, S = input_ids.shape
+        if not torch.is_tensor(labels):
+            labels = torch.as_tensor(labels)
+        if tuple(labels.shape) != (B, S):
+            raise ValueError(f"labels {tuple(labels.shape)} must have the shape of input_ids {(B, S)}")
+        if validate:
+            lc = labels.detach().cpu().to(torch.int64)
+            bad = (lc != -100) & ((lc < 0) | (lc >= V))
+            if bool(bad.any()):
+                raise ValueError(f"labels must be in [0, {V}) or -100; found {int(lc[bad][0])}")
+        left_pad, am_dev = self._left_pad(attention_mask, B, S, validate)
+        Smax = _round_up(S, 256)
+        skey, st = self._llm_state(B, Smax, state_slot)
+        st["counters"].zero_()
+        if left_pad is None:
+            st["left_pad"].zero_()
+        else:
+            st["left_pad"].copy_(left_pad)
+        self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if am_dev is not None:
+            ops.input_check(input_ids.to(self.device, torch.int64).contiguous(), V, None, 0, None, 0, None, self._input_flags,
+                            attn_mask=am_dev)
+        am = None if attention_mask is None else (attention_mask != 0).to(self.device)
+        tgt = score_targets(input_ids.to(self.device), labels.to(self.device), self.crop_tokens_ids, am)       # [B, S - 1]
+        token_lp = torch.zeros((B, S), dtype=torch.float32, device=self.device)
+        sum_lp = torch.zeros((B,), dtype=torch.float32, device=self.device)
+        n_tok = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate):
+            self._prefill(embeds, st, Smax, b0, prune=False)
+            self._score_rows(embeds.view((b1 - b0) * S, C_l), tgt[b0:b1], b0, S, validate, token_lp, sum_lp, n_tok)
+        loss = -(sum_lp.sum() / n_tok.sum().to(torch.float32))
+        return ScoreOutput(token_logprobs=token_lp, sum_logprobs=sum_lp, n_tokens=n_tok, loss=loss,
+                           input_flags=None if validate else self._input_flags)
+
+    def _score_rows(self, h: torch.Tensor, tgt: torch.Tensor, b0: int, S: int, validate: bool, token_lp, sum_lp, n_tok):
+        """Head + cross-entropy of one prefill chunk: ``h`` [sc * S, C] residual stream after the last layer, ``tgt`` [sc, S - 1]
+        targets of rows 0..S-2 (-100 = ignored). validate: only the labelled rows (their list costs one sync); otherwise all."""
+        t = self.config.mllm_config.text_config
+        V, C_l = t.vocab_size, t.hidden_size
+        sc = tgt.shape[0]
+        if S < 2:
+            return
+        src = (torch.arange(sc, device=self.device)[:, None] * S + torch.arange(S - 1, device=self.device)[None, :]).reshape(-1)
+        tg = tgt.reshape(-1)
+        if validate:
+            keep = torch.nonzero(tg != -100).reshape(-1)
+            src, tg = src[keep], tg[keep]
+        R = int(src.numel())
+        if R == 0:
+            return
+        rows = src.to(torch.int32)
+        dest = (rows + b0 * S + 1).to(torch.int32)                  # row t predicts column t + 1 of token_logprobs
+        tg32 = tg.clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32)      # out-of-range labels stay out of range
+        xn = self._buf(("score",), "xn", (R, C_l))
+        ops.gather_rmsnorm(h, rows, self.final_norm, t.rms_norm_eps, xn)
+        flags = self._input_flags
+        # equal chunks of at most XENT_CHUNK_ROWS rows; a chunk the fused head takes (16-bit, > 64 rows) runs there with a
+        # partials workspace sized to it, any other one as dense [<= 64, V] logits pieces
+        n = -(-R // -(-R // self.XENT_CHUNK_ROWS))
+        strips = ops.lm_head_xent_strips(V)
+        for c0 in range(0, R, n):
+            c1 = min(R, c0 + n)
+            if ops.lm_head_xent_takes(self.dtype, c1 - c0, V, C_l):
+                part = self._buf(("score",), "partials", ((c1 - c0) * strips * 2,), torch.float32)
+                tl = self._buf(("score",), "tgt_logit", (c1 - c0,), torch.float32)
+                ops.lm_head_xent(xn[c0:c1], self.lm_head, tg32[c0:c1], part, tl)
+                ops.xent_combine(tg32[c0:c1], dest[c0:c1], S, token_lp, sum_lp, n_tok, V, partials=part, target_logit=tl,
+                                 flags=flags)
+                continue
+            d = self.XENT_DENSE_ROWS
+            logits = self._buf(("score",), "logits", (min(d, c1 - c0), _round_up(V, 64)))
+            for r0 in range(c0, c1, d):
+                r1 = min(c1, r0 + d)
+                ops.gemm(xn[r0:r1], self.lm_head, logits[:r1 - r0])
+                ops.xent_combine(tg32[r0:r1], dest[r0:r1], S, token_lp, sum_lp, n_tok, V, logits=logits[:r1 - r0], flags=flags)
 
     @_on_model_device
     @torch.no_grad()

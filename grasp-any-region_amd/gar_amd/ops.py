@@ -647,3 +647,52 @@ def input_check(input_ids, vocab: int, counts, n_rows: int, spans, span_len: int
 
 def counter_add(counters, delta: int):
     check(lib().gar_counter_add(ptr(counters), counters.numel(), delta, stream()), "gar_counter_add")
+
+
+# ---- caption scoring (GARModel.score; include/gar_hip.h, gar_gather_rmsnorm / gar_lm_head_xent / gar_xent_combine) --------
+def gather_rmsnorm(x, rows, w, eps: float, out):
+    """out[r] = RMSNorm(x[rows[r]]; w): ``x`` [M, D] (row-strided view allowed), ``rows`` int32 [R] (device), ``out`` [R, D]."""
+    M, D, ldx = _rows(x)
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (rows.numel(), D)
+    check(lib(x.dtype).gar_gather_rmsnorm(dtype_code(x.dtype), ptr(x), ldx, M, ptr(rows), rows.numel(), ptr(w), ptr(out), D,
+                                          eps, stream()), "gar_gather_rmsnorm")
+    return out
+
+
+def lm_head_xent_takes(dtype: torch.dtype, R: int, V: int, C: int) -> bool:
+    """True when the fused lm_head + cross-entropy tile GEMM takes R rows (16-bit, R > 64, C % 64 == 0)."""
+    return bool(lib(dtype).gar_lm_head_xent_takes(dtype_code(dtype), int(R), int(V), int(C)))
+
+
+def lm_head_xent_strips(V: int) -> int:
+    return int(lib().gar_lm_head_xent_strips(int(V)))
+
+
+def lm_head_xent(a, w, targets, partials, target_logit):
+    """The fused head: ``a`` [R, C] normed rows, ``w`` lm_head [V, C], ``targets`` int32 [R]; writes ``partials`` f32
+    [R, strips, 2] (per 64-column strip: max, sum exp(x - max)) and ``target_logit`` f32 [R]. No [R, V] logits."""
+    R, Cc = a.shape
+    V = w.shape[0]
+    assert a.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == Cc
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.numel() == R
+    assert partials.dtype == torch.float32 and partials.is_contiguous() and partials.numel() >= R * lm_head_xent_strips(V) * 2
+    assert target_logit.dtype == torch.float32 and target_logit.is_contiguous() and target_logit.numel() >= R
+    _timed("lm_head_xent", (R * Cc + V * Cc) * a.element_size() + R * lm_head_xent_strips(V) * 8, lambda: check(
+        lib(a.dtype).gar_lm_head_xent(dtype_code(a.dtype), ptr(a), a.stride(0), ptr(w), w.stride(0), R, V, Cc, ptr(targets),
+                                      ptr(partials), ptr(target_logit), stream()), "gar_lm_head_xent"), flops=2.0 * R * V * Cc)
+
+
+def xent_combine(targets, dest, S: int, token_logprobs, sum_logprobs, n_tokens, V: int, partials=None, target_logit=None,
+                 logits=None, flags=None):
+    """logprob of every row's target from the fused head's ``partials`` / ``target_logit``, or from dense ``logits`` [R, ld]
+    (model dtype): scattered to ``token_logprobs``.view(-1)[dest[r]] and accumulated per dest // S into ``sum_logprobs`` (f32)
+    and ``n_tokens`` (int32). Targets -100 are ignored; other targets outside [0, V) too, with bit 32 OR-ed into ``flags``."""
+    R = targets.numel()
+    assert targets.dtype == torch.int32 and dest.dtype == torch.int32 and dest.numel() == R
+    assert token_logprobs.dtype == sum_logprobs.dtype == torch.float32 and n_tokens.dtype == torch.int32
+    dt = logits.dtype if logits is not None else torch.bfloat16
+    strips = 0 if partials is None else lm_head_xent_strips(V)
+    check(lib(dt).gar_xent_combine(dtype_code(dt), ptr(partials), strips, ptr(target_logit), ptr(logits),
+                                   0 if logits is None else logits.stride(0), R, int(V), ptr(targets), ptr(dest), int(S),
+                                   ptr(token_logprobs), ptr(sum_logprobs), ptr(n_tokens), ptr(flags), stream()),
+          "gar_xent_combine")

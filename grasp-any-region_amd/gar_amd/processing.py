@@ -420,3 +420,23 @@ class GARProcessor:
         out["input_ids"] = torch.tensor(enc["input_ids"], dtype=torch.int64)
         out["attention_mask"] = torch.tensor(enc["attention_mask"], dtype=torch.int64)
         return out
+
+
+def append_target(sample: dict, target_ids, eos_token_id=None) -> dict:
+    """``sample`` (a dataset item: ``input_ids`` [1, S], optionally ``attention_mask``) with ``target_ids`` (and
+    ``eos_token_id``) appended to ``input_ids``, ``labels`` = -100 over the prompt and the ids over the target, and the
+    ``attention_mask`` extended with ones: what GARModel.forward / score take to score a caption for the region."""
+    import torch
+    ids = sample["input_ids"]
+    tgt = [int(t) for t in (target_ids.tolist() if hasattr(target_ids, "tolist") else target_ids)]
+    if eos_token_id is not None:
+        tgt.append(int(eos_token_id))
+    B = ids.shape[0]
+    add = torch.tensor(tgt, dtype=ids.dtype, device=ids.device).reshape(1, -1).expand(B, -1)
+    out = dict(sample)
+    out["input_ids"] = torch.cat([ids, add], 1)
+    out["labels"] = torch.cat([torch.full_like(ids, -100), add], 1)
+    if sample.get("attention_mask") is not None:
+        am = sample["attention_mask"]
+        out["attention_mask"] = torch.cat([am, torch.ones((B, len(tgt)), dtype=am.dtype, device=am.device)], 1)
+    return out

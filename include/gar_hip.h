@@ -397,6 +397,35 @@ int gar_resize_nearest_tiles(int dtype, const uint8_t* src, void* out, int H, in
                              int ncw, int tile0, const int32_t* xi, const int32_t* yi, float mean, float stdv,
                              gar_stream_t stream);
 
+/* Caption scoring: GARModel.forward(mode="loss") / score(). Replaces the head of the reference's loss path,
+ * `outputs = self._llm_forward(..., labels=labels)` (modeling_gar.py:205-222 -> HF LlamaForCausalLM.forward: final norm,
+ * lm_head, `logits.float()`, shift-by-one cross-entropy with ignore_index -100), without a [rows, V] logits tensor.
+ *
+ * gar_gather_rmsnorm: y[r, :] = LlamaRMSNorm(x[rows[r], :]; w) for the R scored rows (rows int32, device) of the residual
+ *   stream x [M, D] (row stride ldx); y contiguous [R, D]. Equal to gar_rmsnorm on the gathered rows bit for bit; an index
+ *   outside [0, M) gives a zero row.
+ * gar_lm_head_xent: the persistent 256 x 256 tile GEMM A [R, C] x W [V, C]^T (16-bit only, R > 64, C % 64 == 0, operands
+ *   < 4 GiB: gar_lm_head_xent_takes) whose epilogue stores no logits. Per row and 64-column strip it writes
+ *   partials[r][s] = (max x, sum exp(x - max)) in f32 over the strip's logits x rounded to the 16-bit type (columns >= V
+ *   masked; a strip wholly past V holds (-inf, 0)), strips = gar_lm_head_xent_strips(V) = 4 ceil(V / 256); the lane whose
+ *   strip holds column targets[r] writes that rounded logit to target_logit[r] (nothing is written for a target outside
+ *   [0, V)). GAR_ERR_UNSUPPORTED (nothing launched) when the shape is not taken.
+ * gar_xent_combine: per row, logprob = logit[t] - logsumexp over the row, t = targets[r], from the partials (logits NULL)
+ *   or from dense logits [R, ld] of the library's dtype (f32 / the 16-bit type; ld >= V); token_logprobs[dest[r]] = logprob,
+ *   sum_logprobs[dest[r] / S] += logprob, n_tokens[dest[r] / S] += 1 (float / int32 atomics: the f32 sum order is not
+ *   fixed). targets == -100: the row is ignored. Any other target outside [0, V) is ignored too and ORs 32
+ *   (GAR_SCORE_LABEL_RANGE) into flags[0] (nullable). */
+#define GAR_SCORE_LABEL_RANGE 32
+int gar_gather_rmsnorm(int dtype, const void* x, int64_t ldx, int M, const int32_t* rows, int R, const void* w, void* y, int D,
+                       float eps, gar_stream_t stream);
+int gar_lm_head_xent_takes(int dtype, int R, int V, int C);
+int gar_lm_head_xent_strips(int V);
+int gar_lm_head_xent(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, int R, int V, int C,
+                     const int32_t* targets, float* partials, float* target_logit, gar_stream_t stream);
+int gar_xent_combine(int dtype, const float* partials, int strips, const float* target_logit, const void* logits, int64_t ld,
+                     int R, int V, const int32_t* targets, const int32_t* dest, int S, float* token_logprobs,
+                     float* sum_logprobs, int32_t* n_tokens, int32_t* flags, gar_stream_t stream);
+
 /* COCO compressed run-length mask -> row-major [h, w] bytes (host memory, CPU): what `pycocotools.mask.decode`
  * does for the `mask_rles` / `segmentation` entries the benchmark loops read (evaluation/GAR-Bench/inference.py:142-145,
  * evaluation/DLC-Bench/inference.py:121-122). Returns the foreground pixel count, or a negative error code. */
