@@ -32,6 +32,11 @@ def base_parser(description):
     ap.add_argument("--decode_weight_dtype", choices=("auto", "fp8"), default="auto",
                     help="weights of the decode GEMVs: auto = the model dtype; fp8 = OCP e4m3 copies with one scale per output row "
                          "(16-bit models, decode batches <= 64 rows; the prompt phase keeps 16-bit weights)")
+    ap.add_argument("--num_return_sequences", type=int, default=1,
+                    help="N > 1: N sampled captions of the region from ONE prompt phase (implies sampling; --seed keys the draws)")
+    ap.add_argument("--temperature", type=float, default=None, help="sampling temperature (implies sampling)")
+    ap.add_argument("--top_p", type=float, default=None, help="nucleus sampling (implies sampling)")
+    ap.add_argument("--top_k", type=int, default=None, help="top-k sampling (implies sampling)")
     ap.add_argument("--synthetic_weights", action="store_true",
                     help="seeded random weights of the named size + the stub tokenizer (plumbing / benchmarking)")
     return ap
@@ -60,5 +65,15 @@ def load(args):
 
 def generation_config(args, processor):
     # transformers.GenerationConfig(max_new_tokens, do_sample=False, eos, pad) of the reference, as a plain dict
-    return dict(max_new_tokens=args.max_new_tokens, do_sample=False, eos_token_id=processor.tokenizer.eos_token_id,
-                pad_token_id=processor.tokenizer.pad_token_id)
+    gc = dict(max_new_tokens=args.max_new_tokens, do_sample=False, eos_token_id=processor.tokenizer.eos_token_id,
+              pad_token_id=processor.tokenizer.pad_token_id)
+    knobs = {k: getattr(args, k, None) for k in ("temperature", "top_p", "top_k")}
+    n = getattr(args, "num_return_sequences", 1)
+    if n != 1 or any(v is not None for v in knobs.values()):           # the reference CLI is greedy: sampling only when asked for
+        gc.update(do_sample=True, num_return_sequences=n, **{k: v for k, v in knobs.items() if v is not None})
+    return gc
+
+
+def sampling_kwargs(args, gc):
+    """generate() keywords that go with :func:`generation_config`: the request's Philox key when it samples"""
+    return dict(seed=args.seed) if gc.get("do_sample") else {}

@@ -4,7 +4,7 @@
 import numpy as np
 from PIL import Image
 
-from _common import base_parser, generation_config, load
+from _common import base_parser, generation_config, load, sampling_kwargs
 
 
 def main():
@@ -24,8 +24,10 @@ def main():
                                  prompt_number=prompt_number, visual_prompt_tokens=prompt_tokens, data_dtype=dtype,
                                  device=args.device)
     data_sample = dataset[0]
-    out = model.generate(**data_sample, generation_config=generation_config(args, processor), return_dict=True)
-    print(processor.tokenizer.decode(out.sequences[0], skip_special_tokens=True).strip())
+    gc = generation_config(args, processor)
+    out = model.generate(**data_sample, generation_config=gc, return_dict=True, **sampling_kwargs(args, gc))
+    for seq in out.sequences:               # one answer, or the --num_return_sequences sampled ones
+        print(processor.tokenizer.decode(seq, skip_special_tokens=True).strip())
 
 
 if __name__ == "__main__":

@@ -172,34 +172,148 @@ __device__ __forceinline__ void pv_update(f32x16 (&o)[NDB], const VF (&vf)[NDB][
     }
 }
 
+// ---- fan-out decode (gar_attention_decode_fanout): N sampled continuations ("siblings") of one prompt -------------------
+// Rows r = b N + i share prompt b's K / V rows (PROMPT cache [B, Hkv, Sp, HD], rows left_pad[b] .. P - 1) and own the rows they
+// generated (SUFFIX cache [R, Hkv, T, HD], rows 0 .. t). One launch, two kinds of block, the same tile loop:
+//   prefix block (split, column block cb, kv head, prompt b): the heads of up to 32 / G siblings are the live MFMA columns
+//     (column c = head c % G of sibling cb (32 / G) + c / G), so the prompt's K / V stream once per column block, not once per row;
+//   suffix block (kv head, row r): the fused step of decode_qkv_args over the row's own suffix rows — G live columns, the new
+//     key / value appended at suffix row t.
+// Every block leaves (m, l, O) partials of one softmax per (row, head): slots 0 .. nsplit - 1 from the prefix splits, slot nsplit
+// from the suffix; decode_combine_kernel merges the nsplit + 1 slots. P and t come from device memory (one graph per bucket).
+struct decode_fan_args {
+    bf16_t* Ks;                 // suffix caches
+    bf16_t* Vs;
+    const int32_t* prefix_len;  // device: P
+    const int32_t* step;        // device: t
+    int B, N, T, nsplit;        // prompts, siblings per prompt, suffix rows per sequence, prefix splits
+};
+// what one block works on: sequence `b` (its left_pad), cache rows kv_lo .. kv_len - 1 of slab Kp / Vp, of which this block
+// takes the 64-kv tiles t0 .. t1 - 1; live columns c < ncols = head c % G of row row0 + c / G; its partial goes to `slot` of `nslots`
+struct decode_work {
+    bf16_t* Kp;
+    bf16_t* Vp;
+    int kv_stride, kv_len, kv_lo, t0, t1, rp, row0, ncols, slot, nslots;
+    bool appends;
+};
+__device__ __forceinline__ decode_work fan_work(const decode_fan_args& fan, bf16_t* K, bf16_t* V, int Sp, const int32_t* left_pad,
+                                                int Hkv, int G, int HD, int kvh, int x) {
+    decode_work w;
+    const int spb = 32 / G, ncb = (fan.N + spb - 1) / spb;                  // siblings per column block, column blocks
+    const int P = min(max(fan.prefix_len[0], 1), Sp), t = min(max(fan.step[0], 0), fan.T - 1);
+    const int nprefix = fan.B * ncb * fan.nsplit;
+    const bool sfx = x >= nprefix;
+    const int b = sfx ? (x - nprefix) / fan.N : x / (fan.nsplit * ncb);
+    const int lp = left_pad ? left_pad[b] : 0;
+    w.rp = max(P - lp + t, 0);                                              // RoPE position of the step's token
+    w.nslots = fan.nsplit + 1;
+    w.appends = sfx;
+    if (sfx) {
+        const int r = x - nprefix;
+        w.Kp = fan.Ks + (((int64_t)r * Hkv + kvh) * (int64_t)fan.T) * HD;
+        w.Vp = fan.Vs + (((int64_t)r * Hkv + kvh) * (int64_t)fan.T) * HD;
+        w.kv_stride = fan.T; w.kv_len = t + 1; w.kv_lo = 0;
+        w.t0 = 0; w.t1 = (t + 64) / 64;
+        w.row0 = r; w.ncols = G; w.slot = fan.nsplit;
+    } else {
+        const int split = x % fan.nsplit, cb = (x / fan.nsplit) % ncb;
+        w.Kp = K + (((int64_t)b * Hkv + kvh) * (int64_t)Sp) * HD;
+        w.Vp = V + (((int64_t)b * Hkv + kvh) * (int64_t)Sp) * HD;
+        w.kv_stride = Sp; w.kv_len = P; w.kv_lo = max(min(lp, P - 1), 0);
+        const int ntiles = (P + 63) / 64, t_lo = w.kv_lo >> 6;
+        const int per = (ntiles - t_lo + fan.nsplit - 1) / fan.nsplit;
+        w.t0 = t_lo + split * per; w.t1 = min(ntiles, w.t0 + per);
+        w.row0 = b * fan.N + cb * spb; w.ncols = min(fan.N - cb * spb, spb) * G; w.slot = split;
+    }
+    return w;
+}
+
+// a block (split, kv head, sequence) of the plain / fused launches on the grid (splits, Hkv, B)
+__device__ __forceinline__ decode_work plain_work(bf16_t* K, bf16_t* V, int kv_stride, const int32_t* kv_len_dev,
+                                                  const int32_t* kv_start, bool fused, int Hkv, int G, int HD, int kvh) {
+    decode_work w;
+    const int split = blockIdx.x, nsplit = gridDim.x, b = blockIdx.z;
+    w.kv_len = kv_len_dev[0] + (fused ? 1 : 0);                 // fused: kv_len_dev is the step's position, the new row included
+    const int ntiles = (w.kv_len + 63) / 64;
+    // left-padded batch: sequence b lives in cache rows kv_lo .. kv_len - 1; the splits divide THAT range
+    w.kv_lo = kv_start ? max(min(kv_start[b], w.kv_len - 1), 0) : 0;
+    const int t_lo = w.kv_lo >> 6;
+    const int per = (ntiles - t_lo + nsplit - 1) / nsplit;
+    w.t0 = t_lo + split * per; w.t1 = min(ntiles, w.t0 + per);
+    w.Kp = K + (((int64_t)b * Hkv + kvh) * (int64_t)kv_stride) * HD;
+    w.Vp = V + (((int64_t)b * Hkv + kvh) * (int64_t)kv_stride) * HD;
+    w.kv_stride = kv_stride;
+    w.rp = max(w.kv_len - 1 - (kv_start ? kv_start[b] : 0), 0);     // fused: RoPE position of the step's token
+    w.row0 = b; w.ncols = G; w.slot = split; w.nslots = nsplit;
+    w.appends = fused;
+    return w;
+}
+
+// merge_waves_store with up to 32 live columns: every wave parks its (O, m, l) in its OWN tile region (its tiles are in
+// registers and consumed; `wave_bytes` apart, [32][HD + 2] f32 fit both head dims), so the merge needs no LDS of its own
+template <int HD>
+__device__ __forceinline__ void merge_waves_store_fan(const f32x16 (&o)[HD / 32], float m_run, float l_run, char* smem, int wave_bytes,
+                                                      float* __restrict__ part, const decode_work& w, int tid, int wave, int l31,
+                                                      int h, int Hkv, int kvh, int G) {
+    static_assert(32 * (HD + 2) * 4 <= HD * 256, "a wave's partial has to fit its tile region");
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (l31 < w.ncols) {
+        float* pp = reinterpret_cast<float*>(smem + wave * wave_bytes) + l31 * (HD + 2);
+#pragma unroll
+        for (int d = 0; d < HD / 32; ++d)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pp[d * 32 + g4 * 8 + h * 4 + e] = o[d][g4 * 4 + e];
+        if (h == 0) { pp[HD] = m_run; pp[HD + 1] = l_tot; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < w.ncols * HD; idx += 256) {
+        const int c = idx / HD, d = idx % HD;
+        const float* r0 = reinterpret_cast<const float*>(smem) + c * (HD + 2);
+        const int ws = wave_bytes / 4;
+        float m = -INFINITY;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) m = fmaxf(m, r0[v * ws + HD]);
+        const float m_use = m == -INFINITY ? 0.f : m;
+        float acc = 0.f, l = 0.f;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const float sc = __builtin_amdgcn_exp2f(r0[v * ws + HD] - m_use);
+            acc += sc * r0[v * ws + d];
+            l += sc * r0[v * ws + HD + 1];
+        }
+        float* pp = part + ((((int64_t)(w.row0 + c / G) * Hkv + kvh) * w.nslots + w.slot) * G + c % G) * (HD + 2);
+        pp[d] = acc;
+        if (d == 0) { pp[HD] = m; pp[HD + 1] = l; }
+    }
+}
+
 #ifndef DA_KV_AUX               /* cache policy of the K / V DMA: 2 = nt — every byte of the cache is read once per step:
                                    B = 64, kv 4750: 105.8 -> 98.2 us (5.88 -> 6.34 TB/s; profiles/r3_decode_nt.txt) */
 #define DA_KV_AUX 2
 #endif
 #define LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
-__global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* __restrict__ Q, bf16_t* K, bf16_t* V,      // K / V: appended to in fused mode
-                                                                 float* __restrict__ part,
-                                                                 int Hq, int Hkv, int kv_stride,
-                                                                 const int32_t* __restrict__ kv_len_dev, const int32_t* __restrict__ kv_start,
-                                                                 bf16_t* __restrict__ O_direct, const decode_qkv_args fa, int64_t q_stride) {
+// FAN: a block of the fan-out launch (decode_fan_args; Q / kv_len_dev unused, K / V the prompt caches, kv_stride their rows)
+template <bool FAN>
+__device__ __forceinline__ void decode_block64(const bf16_t* __restrict__ Q, bf16_t* K, bf16_t* V, float* __restrict__ part,
+    int Hq, int Hkv, int kv_stride, const int32_t* __restrict__ kv_len_dev, const int32_t* __restrict__ kv_start,
+    bf16_t* __restrict__ O_direct, const decode_qkv_args& fa, int64_t q_stride, const decode_fan_args& fan) {
     constexpr int HD = 64, NKD = HD / 16, NDB = HD / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [4 waves][K 8 KiB | V 8 KiB] then red
     float (*red)[8][HD + 2] = reinterpret_cast<float (*)[8][HD + 2]>(smem + 4 * 16384);
-    const int kv_len = kv_len_dev[0] + (fa.raw ? 1 : 0);            // fused: kv_len_dev is the step's position, the new row included
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
-    const int split = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int kvh = blockIdx.y;
     const int G = Hq / Hkv;
+    const decode_work w = FAN ? fan_work(fan, K, V, kv_stride, kv_start, Hkv, G, HD, kvh, blockIdx.x)
+                              : plain_work(K, V, kv_stride, kv_len_dev, kv_start, fa.raw != nullptr, Hkv, G, HD, kvh);
+    const int kv_len = w.kv_len, kv_lo = w.kv_lo, t0 = w.t0, t1 = w.t1, rp = w.rp;
     const int ntiles = (kv_len + 63) / 64;
-    // left-padded batch: sequence b lives in cache rows kv_lo .. kv_len - 1; the splits divide THAT range
-    const int kv_lo = kv_start ? max(min(kv_start[b], kv_len - 1), 0) : 0;
-    const int t_lo = kv_lo >> 6;
-    const int per = (ntiles - t_lo + nsplit - 1) / nsplit;
-    const int t0 = t_lo + split * per, t1 = min(ntiles, t0 + per);
-    bf16_t* Kp = K + (((int64_t)b * Hkv + kvh) * (int64_t)kv_stride) * HD;
-    bf16_t* Vp = V + (((int64_t)b * Hkv + kvh) * (int64_t)kv_stride) * HD;
-    const unsigned slab = (unsigned)kv_stride * HD * 2u;
+    bf16_t* Kp = w.Kp;
+    bf16_t* Vp = w.Vp;
+    const unsigned slab = (unsigned)w.kv_stride * HD * 2u;
     const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)slab, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)slab, 0x00020000);
     char* ks = smem + wave * 16384;
@@ -224,12 +338,14 @@ __global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* _
                                                      offV + (int)(base + (unsigned)i * 1024u), 0, 0, DA_KV_AUX);
     };
     bf16x8 qf[NKD];
-    const int rp = max(kv_len - 1 - (kv_start ? kv_start[b] : 0), 0);         // fused: RoPE position of the step's token
-    if (fa.raw) {
-        load_q_rotated<HD>(qf, fa, b, Hq, Hkv, kvh * G + min(l31, G - 1), l31 < G, h, rp);
+    if (FAN) {                  // column c: head c % G of row row0 + c / G
+        const int c = min(l31, w.ncols - 1);
+        load_q_rotated<HD>(qf, fa, w.row0 + c / G, Hq, Hkv, kvh * G + c % G, l31 < w.ncols, h, rp);
+    } else if (fa.raw) {
+        load_q_rotated<HD>(qf, fa, w.row0, Hq, Hkv, kvh * G + min(l31, G - 1), l31 < G, h, rp);
     } else {
         const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        const bf16_t* qp = Q + ((int64_t)b * Hq + kvh * G + min(l31, G - 1)) * q_stride;
+        const bf16_t* qp = Q + ((int64_t)w.row0 * Hq + kvh * G + min(l31, G - 1)) * q_stride;
 #pragma unroll
         for (int kd = 0; kd < NKD; ++kd)
             qf[kd] = l31 < G ? *reinterpret_cast<const bf16x8*>(qp + kd * 16 + h * 8) : z;
@@ -261,8 +377,8 @@ __global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* _
     if (t < t1) stage(t);
     for (; t < t1; t += 4) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (fa.raw && t == ntiles - 1)           // the tile that holds the step's own row: this wave appends it
-            append_new_kv<HD, true, true>(fa, Kp, Vp, ks, vs, b, Hq, Hkv, kvh, lane,
+        if (w.appends && t == ntiles - 1)           // the tile that holds the step's own row: this wave appends it
+            append_new_kv<HD, true, true>(fa, Kp, Vp, ks, vs, w.row0, Hq, Hkv, kvh, lane,
                                           kv_len - 1, rp, [](int r) { return (r >> 1) & 7; }, [](int r) { return ((r >> 1) & 1) << 2; });
         bf16x8 kf[2][NKD], vf[NDB][4];
 #pragma unroll
@@ -324,7 +440,19 @@ __global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* _
         l_run = l_run * alpha + ps;
         pv_update(o, vf, pf, alpha);
     }
-    merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, b, Hq, Hkv, kvh, G, split, nsplit);
+    if (FAN) merge_waves_store_fan<HD>(o, m_run, l_run, smem, 16384, part, w, tid, wave, l31, h, Hkv, kvh, G);
+    else merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, w.row0, Hq, Hkv, kvh, G, w.slot, w.nslots);
+}
+
+__global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* __restrict__ Q, bf16_t* K, bf16_t* V,      // K / V: appended to in fused mode
+        float* __restrict__ part, int Hq, int Hkv, int kv_stride, const int32_t* __restrict__ kv_len_dev,
+        const int32_t* __restrict__ kv_start, bf16_t* __restrict__ O_direct, const decode_qkv_args fa, int64_t q_stride) {
+    decode_block64<false>(Q, K, V, part, Hq, Hkv, kv_stride, kv_len_dev, kv_start, O_direct, fa, q_stride, decode_fan_args{});
+}
+// grid (B column-blocks nsplit + R, Hkv): K / V the prompt caches [B, Hkv, Sp, HD], left_pad [B] or NULL
+__global__ __launch_bounds__(256, 2) void decode_attn_lds_fan_kernel(bf16_t* K, bf16_t* V, float* __restrict__ part, int Hq, int Hkv, int Sp,
+        const int32_t* __restrict__ left_pad, const decode_qkv_args fa, const decode_fan_args fan) {
+    decode_block64<true>(nullptr, K, V, part, Hq, Hkv, Sp, nullptr, left_pad, nullptr, fa, 0, fan);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -334,29 +462,26 @@ __global__ __launch_bounds__(256, 2) void decode_attn_lds_kernel(const bf16_t* _
 //   wait K(t) [vmcnt: the 16 V pieces behind it may stay out] -> K fragments -> re-arm K with tile t+4 -> QK^T, softmax
 //   wait V(t) [the 16 K pieces just issued may stay out]      -> V fragments -> re-arm V             -> PV
 // 128 KiB + merge buffer per block: one block (4 waves) per CU, the same 128 KiB of loads in flight per CU.
-__global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t* __restrict__ Q, bf16_t* K, bf16_t* V,
-                                                                    float* __restrict__ part,
-                                                                    int Hq, int Hkv, int kv_stride,
-                                                                    const int32_t* __restrict__ kv_len_dev, const int32_t* __restrict__ kv_start,
-                                                                    bf16_t* __restrict__ O_direct, const decode_qkv_args fa, int64_t q_stride) {
+// FAN: a block of the fan-out launch (decode_fan_args; Q / kv_len_dev unused, K / V the prompt caches, kv_stride their rows)
+template <bool FAN>
+__device__ __forceinline__ void decode_block128(const bf16_t* __restrict__ Q, bf16_t* K, bf16_t* V, float* __restrict__ part,
+    int Hq, int Hkv, int kv_stride, const int32_t* __restrict__ kv_len_dev, const int32_t* __restrict__ kv_start,
+    bf16_t* __restrict__ O_direct, const decode_qkv_args& fa, int64_t q_stride, const decode_fan_args& fan) {
     constexpr int HD = 128, NKD = HD / 16, NDB = HD / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [4 waves][K 16 KiB | V 16 KiB] then red
     float (*red)[8][HD + 2] = reinterpret_cast<float (*)[8][HD + 2]>(smem + 4 * 32768);
-    const int kv_len = kv_len_dev[0] + (fa.raw ? 1 : 0);            // fused: kv_len_dev is the step's position, the new row included
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
-    const int split = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int kvh = blockIdx.y;
     const int G = Hq / Hkv;
+    const decode_work w = FAN ? fan_work(fan, K, V, kv_stride, kv_start, Hkv, G, HD, kvh, blockIdx.x)
+                              : plain_work(K, V, kv_stride, kv_len_dev, kv_start, fa.raw != nullptr, Hkv, G, HD, kvh);
+    const int kv_len = w.kv_len, kv_lo = w.kv_lo, t0 = w.t0, t1 = w.t1, rp = w.rp;
     const int ntiles = (kv_len + 63) / 64;
-    // left-padded batch: sequence b lives in cache rows kv_lo .. kv_len - 1; the splits divide THAT range
-    const int kv_lo = kv_start ? max(min(kv_start[b], kv_len - 1), 0) : 0;
-    const int t_lo = kv_lo >> 6;
-    const int per = (ntiles - t_lo + nsplit - 1) / nsplit;
-    const int t0 = t_lo + split * per, t1 = min(ntiles, t0 + per);
-    bf16_t* Kp = K + (((int64_t)b * Hkv + kvh) * (int64_t)kv_stride) * HD;
-    bf16_t* Vp = V + (((int64_t)b * Hkv + kvh) * (int64_t)kv_stride) * HD;
-    const unsigned slab = (unsigned)kv_stride * HD * 2u;
+    bf16_t* Kp = w.Kp;
+    bf16_t* Vp = w.Vp;
+    const unsigned slab = (unsigned)w.kv_stride * HD * 2u;
     const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc((void*)Kp, 0, (int)slab, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)Vp, 0, (int)slab, 0x00020000);
     char* ks = smem + wave * 32768;
@@ -387,12 +512,14 @@ __global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t
                                                      offV + (int)(vbase + (unsigned)i * 1024u), 0, 0, DA_KV_AUX);
     };
     bf16x8 qf[NKD];
-    const int rp = max(kv_len - 1 - (kv_start ? kv_start[b] : 0), 0);         // fused: RoPE position of the step's token
-    if (fa.raw) {
-        load_q_rotated<HD>(qf, fa, b, Hq, Hkv, kvh * G + min(l31, G - 1), l31 < G, h, rp);
+    if (FAN) {                  // column c: head c % G of row row0 + c / G
+        const int c = min(l31, w.ncols - 1);
+        load_q_rotated<HD>(qf, fa, w.row0 + c / G, Hq, Hkv, kvh * G + c % G, l31 < w.ncols, h, rp);
+    } else if (fa.raw) {
+        load_q_rotated<HD>(qf, fa, w.row0, Hq, Hkv, kvh * G + min(l31, G - 1), l31 < G, h, rp);
     } else {
         const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        const bf16_t* qp = Q + ((int64_t)b * Hq + kvh * G + min(l31, G - 1)) * q_stride;
+        const bf16_t* qp = Q + ((int64_t)w.row0 * Hq + kvh * G + min(l31, G - 1)) * q_stride;
 #pragma unroll
         for (int kd = 0; kd < NKD; ++kd)
             qf[kd] = l31 < G ? *reinterpret_cast<const bf16x8*>(qp + kd * 16 + h * 8) : z;
@@ -423,9 +550,9 @@ __global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t
     for (; t < t1; t += 4) {
         const bool more = t + 4 < t1;
         asm volatile("s_waitcnt vmcnt(16)" ::: "memory");          // K(t) landed; the 16 V(t) pieces may still be out
-        const bool own_new = fa.raw && t == ntiles - 1;            // the tile that holds the step's own row (this wave's last tile)
+        const bool own_new = w.appends && t == ntiles - 1;            // the tile that holds the step's own row (this wave's last tile)
         if (own_new)
-            append_new_kv<HD, true, false>(fa, Kp, Vp, ks, vs, b, Hq, Hkv, kvh, lane,
+            append_new_kv<HD, true, false>(fa, Kp, Vp, ks, vs, w.row0, Hq, Hkv, kvh, lane,
                                            kv_len - 1, rp, [](int r) { return r & 15; }, [](int r) { return (r & 3) << 2; });
         f32x16 s[2];
         {
@@ -487,7 +614,7 @@ __global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t
         if (more) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (own_new)                            // (the key row's global stores sit behind vmcnt(0) too: `more` is false here)
-            append_new_kv<HD, false, true>(fa, Kp, Vp, ks, vs, b, Hq, Hkv, kvh, lane,
+            append_new_kv<HD, false, true>(fa, Kp, Vp, ks, vs, w.row0, Hq, Hkv, kvh, lane,
                                            kv_len - 1, rp, [](int r) { return r & 15; }, [](int r) { return (r & 3) << 2; });
         bf16x8 vf[NDB][4];
 #pragma unroll
@@ -500,7 +627,19 @@ __global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t
         __builtin_amdgcn_sched_barrier(0);
         pv_update(o, vf, pf, alpha);
     }
-    merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, b, Hq, Hkv, kvh, G, split, nsplit);
+    if (FAN) merge_waves_store_fan<HD>(o, m_run, l_run, smem, 32768, part, w, tid, wave, l31, h, Hkv, kvh, G);
+    else merge_waves_store<HD>(o, m_run, l_run, red, part, O_direct, tid, wave, l31, h, w.row0, Hq, Hkv, kvh, G, w.slot, w.nslots);
+}
+
+__global__ __launch_bounds__(256, 1) void decode_attn_lds128_kernel(const bf16_t* __restrict__ Q, bf16_t* K, bf16_t* V,      // K / V: appended to in fused mode
+        float* __restrict__ part, int Hq, int Hkv, int kv_stride, const int32_t* __restrict__ kv_len_dev,
+        const int32_t* __restrict__ kv_start, bf16_t* __restrict__ O_direct, const decode_qkv_args fa, int64_t q_stride) {
+    decode_block128<false>(Q, K, V, part, Hq, Hkv, kv_stride, kv_len_dev, kv_start, O_direct, fa, q_stride, decode_fan_args{});
+}
+// grid (B column-blocks nsplit + R, Hkv): K / V the prompt caches [B, Hkv, Sp, HD], left_pad [B] or NULL
+__global__ __launch_bounds__(256, 1) void decode_attn_lds128_fan_kernel(bf16_t* K, bf16_t* V, float* __restrict__ part, int Hq, int Hkv, int Sp,
+        const int32_t* __restrict__ left_pad, const decode_qkv_args fa, const decode_fan_args fan) {
+    decode_block128<true>(nullptr, K, V, part, Hq, Hkv, Sp, nullptr, left_pad, nullptr, fa, 0, fan);
 }
 
 // one wave per (b, q head): lanes over splits for the statistics, then over d for the accumulation
@@ -621,6 +760,59 @@ extern "C" int gar_attention_decode_qkv(int dtype, const void* qkv, const float*
     const decode_qkv_args fa = {(const bf16_t*)qkv, cos, sin, q_scale, qk_strip_order ? 1 : 0};
     return launch_decode("attention_decode_qkv", nullptr, hd, Kc, Vc, O, B, Hq, Hkv, hd, Smax, pos_dev, left_pad, max_splits,
                          workspace, fa, stream);
+}
+
+// ---- gar_attention_decode_fanout: see decode_fan_args --------------------------------------------------------------------
+extern "C" int64_t gar_attention_decode_fanout_workspace(int R, int Hq, int hd, int max_splits) {
+    return gar_attention_decode_workspace(R, Hq, hd, max_splits + 1);          // the prefix splits' slots and the suffix slot
+}
+
+extern "C" int gar_attention_decode_fanout(int dtype, const void* qkv, const float* cos, const float* sin, const void* Kp,
+                                           const void* Vp, void* Ksuf, void* Vsuf, void* O, int B, int N, int Hq, int Hkv, int hd,
+                                           int Sp, int T, const int32_t* prefix_len_dev, const int32_t* step_dev,
+                                           const int32_t* left_pad, float q_scale, int qk_strip_order, int max_splits,
+                                           void* workspace, gar_stream_t stream) {
+    const char* what = "attention_decode_fanout";
+    GAR_CHECK_ARG(qkv && cos && sin && Kp && Vp && Ksuf && Vsuf && O && prefix_len_dev && step_dev, "%s: null pointer", what);
+    GAR_CHECK_ARG(N > 0 && (int64_t)B * N <= 65535, "%s: need N >= 1 rows per prompt and B * N <= 65535", what);
+    if (int e = check_decode_args(what, qkv, nullptr, B, Hq, Hkv, hd, Sp)) return e;
+    GAR_CHECK_ARG(T > 0 && T % 64 == 0, "%s: T must be a positive multiple of 64", what);
+    GAR_CHECK_ARG(workspace && max_splits > 0 && max_splits < 64, "%s: workspace / max_splits (1..63)", what);
+    if (dtype != GAR_BF16) {
+        gar_set_error("%s: 16-bit only (parity mode decodes N copies of the prompt's cache rows with the plain step)", what);
+        return GAR_ERR_UNSUPPORTED;
+    }
+    if ((int64_t)max(Sp, T) * hd * 2 >= ((int64_t)1 << 31)) {
+        gar_set_error("%s: %d rows x head_dim %d exceed the 2 GiB per-slab range of the DMA-staged kernels", what, max(Sp, T), hd);
+        return GAR_ERR_UNSUPPORTED;
+    }
+    const int G = Hq / Hkv, spb = 32 / G, ncb = (N + spb - 1) / spb, R = B * N;
+    const decode_qkv_args fa = {(const bf16_t*)qkv, cos, sin, q_scale, qk_strip_order ? 1 : 0};
+    const decode_fan_args fan = {(bf16_t*)Ksuf, (bf16_t*)Vsuf, prefix_len_dev, step_dev, B, N, T, max_splits};
+    const dim3 grid((unsigned)(B * ncb * max_splits + R), Hkv);
+    hipStream_t s = (hipStream_t)stream;
+    static gar_once_per_device attr_once;
+    attr_once.run([&] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_lds_fan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * 16384);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_lds128_fan_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
+    });
+    // (the prompt caches are only read: the fan kernels append to the suffix caches)
+    if (hd == 64)
+        hipLaunchKernelGGL(decode_attn_lds_fan_kernel, grid, dim3(256), 4 * 16384, s, (bf16_t*)const_cast<void*>(Kp),
+                           (bf16_t*)const_cast<void*>(Vp), (float*)workspace, Hq, Hkv, Sp, left_pad, fa, fan);
+    else
+        hipLaunchKernelGGL(decode_attn_lds128_fan_kernel, grid, dim3(256), 4 * 32768, s, (bf16_t*)const_cast<void*>(Kp),
+                           (bf16_t*)const_cast<void*>(Vp), (float*)workspace, Hq, Hkv, Sp, left_pad, fa, fan);
+    if (hd == 64)
+        hipLaunchKernelGGL((decode_combine_kernel<64>), dim3(Hq, R), dim3(64), 0, s, (const float*)workspace, (bf16_t*)O, Hq, Hkv,
+                           max_splits + 1);
+    else
+        hipLaunchKernelGGL((decode_combine_kernel<128>), dim3(Hq, R), dim3(64), 0, s, (const float*)workspace, (bf16_t*)O, Hq, Hkv,
+                           max_splits + 1);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
 }
 
 // =====================================================================================================================

@@ -67,7 +67,10 @@ SIGNATURES = {
     "gar_attention_decode": ([_i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
     "gar_attention_decode_qkv": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp], _i),
     "gar_kv_quantize_fp8": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "gar_attention_decode_fp8_workspace": ([_i, _i, _i, _i], _i64),
+    "gar_attention_decode_fanout_workspace": ([_i, _i, _i, _i], _i64),
+    "gar_attention_decode_fanout": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i,
+                                     _vp, _vp], _i),
+    "gar_attention_decode_fp8_workspace":([_i, _i, _i, _i], _i64),
     "gar_attention_decode_fp8": ([_i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
     "gar_attention_decode_qkv_fp8": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp],
                                      _i),

@@ -136,9 +136,51 @@ class _OverlaidOptions:
         return self._over[k] if k in self._over else self._base(k, d)
 
 
+def _option_reader(generation_config, generate_kwargs):
+    """``get(name, default)`` over the options of a request: a GenerationConfig object or a dict, with the keyword arguments of the
+    call laid over it (HF: `generate(generation_config, **kwargs)`). None when the request carries no option at all."""
+    gc = generation_config
+    if generate_kwargs:
+        # the reference forwards **generate_kwargs to HF's generate (modeling_gar.py:418-426), which lays them OVER the generation
+        # config: the same here — an option passed as a keyword is read (and refused if not built) like one in the config, never
+        # swallowed; a keyword that is no generation option at all is an error as it is in HF (ADVICE r5)
+        unknown = sorted(k for k in generate_kwargs if k not in _GENERATION_KWARGS)
+        if unknown:
+            raise TypeError(f"generate() got unexpected keyword arguments {unknown} (generation options: see GenerationConfig)")
+        base = gc
+        base_get = (lambda k, d=None: d) if base is None else \
+            ((lambda k, d=None: base.get(k, d)) if isinstance(base, dict) else (lambda k, d=None: getattr(base, k, d)))
+        gc = _OverlaidOptions(base_get, dict(generate_kwargs))
+    if gc is None:
+        return None
+    return gc.get if isinstance(gc, (dict, _OverlaidOptions)) else (lambda k, d=None: getattr(gc, k, d))
+
+
+def _num_return_sequences(get, kv_cache_dtype=None) -> int:
+    """N of a request (HF: ``sequences`` is [B * N, n], row b * N + i = sample i of prompt b). N > 1 needs do_sample = True — without
+    it :func:`_refuse_non_greedy` refuses the option as before — and the 16-bit KV cache."""
+    v = get("num_return_sequences")
+    if v is None:
+        return 1
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"`num_return_sequences` has to be an integer >= 1, but is {v!r}")
+    if v > 1 and get("do_sample", False) and kv_cache_dtype == "fp8":
+        raise hip.GarError(f"num_return_sequences={v} with kv_cache_dtype='fp8' is not implemented (the shared-prefix decode "
+                           "attention reads 16-bit caches)")
+    return v
+
+
+def _fanout_rows(b0: int, b1: int, N: int):
+    """rows of the expanded batch that prompts b0 .. b1 - 1 fan out to: prompt b owns rows b * N .. b * N + N - 1, and row r is
+    also the Philox row counter of its draws — what the replicated batch (repeat_interleave(N) of the inputs) would use"""
+    return b0 * N, b1 * N
+
+
 def _refuse_non_greedy(get):
     for name, neutral in _NEUTRAL_GENERATION_OPTIONS.items():
         v = get(name)
+        if name == "num_return_sequences" and get("do_sample", False):
+            continue                                        # sampling: read by _num_return_sequences
         if not any((v is n) or (n is not None and not isinstance(v, bool) and v == n) for n in neutral):
             raise hip.GarError(f"generation option {name}={v!r} is not implemented (greedy search only: it would change the tokens "
                                f"and is refused rather than ignored)")
@@ -353,6 +395,9 @@ class GenerationPipeline:
             if slot in self.done:
                 main.wait_event(self.done[slot])            # the prefill overwrites that slot's cache, counters and token buffer
             pend = m.generate_begin(**sample, **self.kwargs, state_slot=slot)
+            if pend.N > 1:
+                raise hip.GarError(f"GenerationPipeline / generate_pipelined: num_return_sequences={pend.N} is not implemented "
+                                   "(call generate)")
             pend.ready = torch.cuda.Event()
             pend.ready.record(main)
         if self.prev is not None:
@@ -1016,11 +1061,13 @@ class GARModel:
         return embeds
 
     # ---- Llama (A12) --------------------------------------------------------------------------------------------------
-    def _llm_state(self, B: int, Smax: int, slot: int = 0):
+    def _llm_state(self, B: int, Smax: int, slot: int = 0, fan=None):
         """KV cache + counters of one (B, Smax) bucket. ``slot``: independent copies of the same bucket — the pipelined driver
-        (generate_pipelined) decodes batch i from one slot while batch i + 1 prefills into the other."""
+        (generate_pipelined) decodes batch i from one slot while batch i + 1 prefills into the other. ``fan`` = (prompts, Sp): the
+        B rows are the continuations of a num_return_sequences request, Kc / Vc hold their generated tokens only (Smax = T rows),
+        counters = [t, -, step, P]; the prompts' rows stay in the (prompts, Sp) state (:meth:`_generate_begin_fanout`)."""
         t = self.config.mllm_config.text_config
-        key = ("llm", B, Smax, slot)
+        key = ("llm", B, Smax, slot) if fan is None else ("llm", B, Smax, slot, fan)
         if key in self._llm_lru:
             self._llm_lru.remove(key)
         self._llm_lru.append(key)
@@ -1205,10 +1252,11 @@ class GARModel:
         return t
 
     def _head(self, last_rows: torch.Tensor, B: int, out_tokens, st, cur=None, normed: Optional[torch.Tensor] = None,
-              finished=None, row0: int = 0, decode: bool = False):
+              finished=None, row0: int = 0, decode: bool = False, pick: bool = True):
         """final RMSNorm + lm_head + greedy argmax of the given [B, C] rows (row-strided view allowed). ``normed``: the
         rows after the final norm, when the caller's last launch produced them already (split-K decode path). ``decode``: a
-        decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token."""
+        decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token. ``pick`` False:
+        the logits only — the caller draws the tokens (N draws per prompt row: _generate_begin_fanout)."""
         gemm = self._gemm_w8 if decode and self.w_fp8 else ops.gemm
         cur = st["cur"] if cur is None else cur
         t = self.config.mllm_config.text_config
@@ -1225,6 +1273,8 @@ class GARModel:
         else:
             ops.rmsnorm(last_rows, self.final_norm, t.rms_norm_eps, out=xn)
             gemm(xn, self.lm_head, logits)
+        if not pick:
+            return logits
         fin = st["finished"] if finished is None else finished
         if st.get("sampling"):
             ops.sample(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, st["sample_params"], st["sample_seed"],
@@ -1248,8 +1298,14 @@ class GARModel:
         cos, sin = self._llm_rope(Smax)
         q_scale = (hd ** -0.5) * LOG2E
         pos_dev, kvlen_dev = st["counters"][0:1], st["counters"][1:2]
-        nsplit = max(1, min(self.DECODE_ATTN_MAX_SPLITS, self.DECODE_ATTN_BLOCKS // max(1, B * Hkv)))
-        dws = self._buf(key, "attn_ws", (ops.attention_decode_workspace(B, Hq, hd, nsplit),), torch.uint8)
+        fan = st.get("fan")         # B = prompts x N rows over shared prompt caches: the prefix splits count over the prompts
+        if fan:
+            blocks = fan["B"] * Hkv * -(-fan["N"] // max(1, 32 // (Hq // Hkv)))
+            nsplit = max(1, min(self.DECODE_ATTN_MAX_SPLITS, self.DECODE_ATTN_BLOCKS // blocks))
+            dws = self._buf(key, "attn_ws_fan", (ops.attention_decode_fanout_workspace(B, Hq, hd, nsplit),), torch.uint8)
+        else:
+            nsplit = max(1, min(self.DECODE_ATTN_MAX_SPLITS, self.DECODE_ATTN_BLOCKS // max(1, B * Hkv)))
+            dws = self._buf(key, "attn_ws", (ops.attention_decode_workspace(B, Hq, hd, nsplit),), torch.uint8)
         ops.embed_lookup(st["cur"], self.E, h)
         gemm = self._gemm_w8 if self.w_fp8 else ops.gemm       # the weight GEMVs: e4m3 copies (decode_weight_dtype="fp8") or 16-bit
         bf16 = self.dtype in HALF_DTYPES
@@ -1285,7 +1341,11 @@ class GARModel:
                     ops.rmsnorm(h, self.unit_rms if use_folded_w else ly["ln1"], t.rms_norm_eps, out=xn)
                 gemm(xn, ly["qkv_f"] if use_folded_w else ly["qkv"], qkv)
             # bf16: RoPE, q scale and the cache append run inside the attention launch (one launch instead of two)
-            if self.kv_fp8:     # the fp8 cache has only the fused form: the new row is quantized inside the launch
+            if fan:             # prompt rows once per kv head for up to 32 / G siblings, then each row's own generated rows
+                ops.attention_decode_fanout(qkv, cos, sin, fan["Kp"][li], fan["Vp"][li], st["Kc"][li], st["Vc"][li], att, fan["B"],
+                                            fan["N"], Hq, Hkv, hd, fan["Sp"], Smax - fan["Sp"], st["counters"][3:4],
+                                            st["counters"][0:1], q_scale, nsplit, dws, left_pad=fan["left_pad"], strip_order=strip)
+            elif self.kv_fp8:   # the fp8 cache has only the fused form: the new row is quantized inside the launch
                 ops.attention_decode_qkv_fp8(qkv, cos, sin, st["Kc"][li], st["Vc"][li], st["Ks"][li], st["Vs"][li], att, B, Hq, Hkv,
                                              hd, Smax, pos_dev, q_scale, nsplit, dws, left_pad=st["left_pad"], strip_order=strip)
             elif not (self.DECODE_ATTN_TAKES_QKV and
@@ -1454,21 +1514,11 @@ class GARModel:
         ``forced_tokens`` [B, n] (tests): teacher forcing — ``sequences`` / ``logits`` still report what the model chose at
         every step, but the token fed back as step j's input is ``forced_tokens[:, j]``, so two models (bf16 vs f32) can be
         compared on identical contexts over a whole caption."""
-        gc = generation_config
         sampling = None
-        if generate_kwargs:
-            # the reference forwards **generate_kwargs to HF's generate (modeling_gar.py:418-426), which lays them OVER the generation
-            # config: the same here — an option passed as a keyword is read (and refused if not built) like one in the config, never
-            # swallowed; a keyword that is no generation option at all is an error as it is in HF (ADVICE r5)
-            unknown = sorted(k for k in generate_kwargs if k not in _GENERATION_KWARGS)
-            if unknown:
-                raise TypeError(f"generate() got unexpected keyword arguments {unknown} (generation options: see GenerationConfig)")
-            base = gc
-            base_get = (lambda k, d=None: d) if base is None else \
-                ((lambda k, d=None: base.get(k, d)) if isinstance(base, dict) else (lambda k, d=None: getattr(base, k, d)))
-            gc = _OverlaidOptions(base_get, dict(generate_kwargs))
-        if gc is not None:
-            get = gc.get if isinstance(gc, (dict, _OverlaidOptions)) else (lambda k, d=None: getattr(gc, k, d))
+        N = 1
+        get = _option_reader(generation_config, generate_kwargs)
+        if get is not None:
+            N = _num_return_sequences(get, self.kv_cache_dtype)
             _refuse_non_greedy(get)
             if get("do_sample", False):
                 sampling = _sampling_options(get)
@@ -1481,7 +1531,12 @@ class GARModel:
         max_new_tokens = int(max_new_tokens or 64)
         cfg = self.config
         B, S = input_ids.shape
-        self._check_decode_rows(B, "generate")
+        self._check_decode_rows(B * N, "generate")
+        if N > 1:
+            return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
+                                               max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
+                                               return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
+                                               state_slot)
         # attention_mask is forwarded to the Llama generate by the reference (modeling_gar.py:418-426). A LEFT-padded batch
         # (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a
         # sequence keeps its rows in the padded layout, its RoPE positions count from its first real token and the padding
@@ -1494,31 +1549,7 @@ class GARModel:
         Smax = _round_up(S + max_new_tokens, 256)
         skey, st = self._llm_state(B, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (B, Smax), torch.int64, zero=True)[:, :max_new_tokens]
-        st["counters"].zero_()
-        if left_pad is None:
-            st["left_pad"].zero_()
-        else:
-            st["left_pad"].copy_(left_pad)
-        eos_list = []
-        if eos_token_id is not None:
-            eos_list = [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])]
-        # the stopping criterion lives on the device (gar_argmax latches each row's first eos step): fills take their value as a
-        # kernel argument, the id table is one small upload
-        eos_on_device = len(eos_list) <= self.MAX_EOS_IDS
-        st["finished"].fill_(-1)
-        st["done_count"].zero_()
-        st["eos_ids"].fill_(-1)
-        if eos_list and eos_on_device:
-            st["eos_ids"][:len(eos_list)].copy_(self._upload(eos_list, torch.int64))
-        st["sampling"] = sampling is not None
-        if sampling is not None:
-            if seed is None:          # HF draws from torch's global generator: so does the key of this request (torch.manual_seed reproduces it)
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
-                if torch.distributed.is_available() and torch.distributed.is_initialized():
-                    # identically seeded data-parallel ranks must not replay one stream on different regions
-                    seed = (seed ^ (0x9E3779B97F4A7C15 * (torch.distributed.get_rank() + 1))) & (2 ** 62 - 1)
-            st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0], torch.float32))
-            st["sample_seed"].copy_(self._upload([int(seed)], torch.int64, cache=False))
+        eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
         self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -1547,7 +1578,104 @@ class GARModel:
         return _PendingGeneration(eos_on_device=eos_on_device, st=st, skey=skey, B=B, Smax=Smax, V=V, out_tokens=out_tokens, max_new_tokens=max_new_tokens,
                                   eos=eos, eos_first=eos_first, pad_token_id=pad_token_id, return_logits=return_logits,
                                   all_logits=all_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
-                                  sync_every=sync_every, input_flags=self._input_flags)
+                                  sync_every=sync_every, input_flags=self._input_flags, N=1)
+
+    def _arm_state(self, st, left_pad, eos_token_id, sampling, seed):
+        """A state's request words before the prompt phase: counters, left_pad, the stopping criterion's latches and eos table, the
+        sampling parameters and Philox key. Returns (eos ids, whether the device holds them)."""
+        st["counters"].zero_()
+        if left_pad is None:
+            st["left_pad"].zero_()
+        else:
+            st["left_pad"].copy_(left_pad)
+        eos_list = []
+        if eos_token_id is not None:
+            eos_list = [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])]
+        # the stopping criterion lives on the device (gar_argmax latches each row's first eos step): fills take their value as a
+        # kernel argument, the id table is one small upload
+        eos_on_device = len(eos_list) <= self.MAX_EOS_IDS
+        st["finished"].fill_(-1)
+        st["done_count"].zero_()
+        st["eos_ids"].fill_(-1)
+        if eos_list and eos_on_device:
+            st["eos_ids"][:len(eos_list)].copy_(self._upload(eos_list, torch.int64))
+        st["sampling"] = sampling is not None
+        if sampling is not None:
+            if seed is None:          # HF draws from torch's global generator: so does the key of this request (torch.manual_seed reproduces it)
+                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+                if torch.distributed.is_available() and torch.distributed.is_initialized():
+                    # identically seeded data-parallel ranks must not replay one stream on different regions
+                    seed = (seed ^ (0x9E3779B97F4A7C15 * (torch.distributed.get_rank() + 1))) & (2 ** 62 - 1)
+            st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0], torch.float32))
+            st["sample_seed"].copy_(self._upload([int(seed)], torch.int64, cache=False))
+        return eos_list, eos_on_device
+
+    def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
+                               max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate, return_logits,
+                               sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot):
+        """generate_begin of a num_return_sequences = N > 1 request (do_sample): ONE prompt phase over the B prompts, N first
+        tokens drawn from each prompt's logits, and a state of B * N rows for :meth:`generate_finish` — row b * N + i is sample i
+        of prompt b, its draws counted by (seed, step, b * N + i) as the replicated batch's would be.
+        16-bit models: the rows share the prompt's cache rows (the (B, Sp) state the prefill wrote) and keep only their generated
+        tokens (gar_attention_decode_fanout). f32 parity mode: the prompt's rows are copied into an ordinary (B * N, Smax) state
+        and the plain step decodes it — the N - 1 prompt phases are saved, the cache is not shared."""
+        t = self.config.mllm_config.text_config
+        B, S = input_ids.shape
+        R, V = B * N, t.vocab_size
+        left_pad, am_dev = self._left_pad(attention_mask, B, S, validate)
+        if forced_tokens is not None:
+            forced_tokens = forced_tokens.to(self.device, torch.int64)
+            if forced_tokens.shape[0] != R:
+                raise ValueError(f"forced_tokens must have B * num_return_sequences = {R} rows, got {forced_tokens.shape[0]}")
+        shared = self.dtype in HALF_DTYPES
+        if shared:
+            Sp, T = _round_up(S, 256), _round_up(max_new_tokens, 64)
+            _, pst = self._llm_state(B, Sp, state_slot)
+            skey, st = self._llm_state(R, T, state_slot, fan=(B, Sp))
+            st["fan"] = dict(B=B, N=N, Sp=Sp, Kp=pst["Kc"], Vp=pst["Vc"], left_pad=pst["left_pad"])
+            Smax = Sp + T               # what generate_finish hands to the step: RoPE table rows; T = Smax - Sp
+        else:
+            Sp = Smax = _round_up(S + max_new_tokens, 256)
+            _, pst = self._llm_state(B, Smax, state_slot)
+            skey, st = self._llm_state(R, Smax, state_slot)
+        out_tokens = self._buf(skey, "out_tokens", (R, Smax - Sp if shared else Smax), torch.int64, zero=True)[:, :max_new_tokens]
+        self._arm_state(pst, left_pad, None, None, None)
+        eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed)
+        first_logits = []
+        self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if am_dev is not None:
+            ops.input_check(input_ids.to(self.device, torch.int64).contiguous(), V, None, 0, None, 0, None, self._input_flags,
+                            attn_mask=am_dev)
+        for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
+                                                  feature_replay_video, video_frame_tokens):
+            last = self._prefill(embeds, pst, Sp, b0)
+            lg = self._head(last, b1 - b0, None, pst, pick=False).repeat_interleave(N, 0)      # the SAME logits for the N draws
+            r0, r1 = _fanout_rows(b0, b1, N)
+            ops.sample(lg, V, out_tokens[r0:r1], out_tokens.stride(0), st["counters"][2:3], st["cur"][r0:r1], st["sample_params"],
+                       st["sample_seed"], eos_ids=st["eos_ids"], finished=st["finished"][r0:r1], done_count=st["done_count"],
+                       row_offset=r0)
+            if forced_tokens is not None:
+                st["cur"][r0:r1].copy_(forced_tokens[r0:r1, 0])
+            if return_logits:
+                first_logits.append(lg[:, :V].float())
+        all_logits = [torch.cat(first_logits, 0)] if return_logits else []
+        c = st["counters"]
+        if shared:                      # [t, -, step, P]: the first decode step appends at suffix row 0
+            c[2:3].fill_(1)
+            c[3:4].fill_(S)
+        else:                           # the prompts' cache rows, N times; counters as generate_begin leaves them
+            L, Hkv, hd = t.num_hidden_layers, t.num_key_value_heads, t.head_dim
+            for name in ("Kc", "Vc"):
+                st[name].view(L, B, N, Hkv, Smax, hd).copy_(pst[name][:, :, None])
+            st["left_pad"].copy_(pst["left_pad"].repeat_interleave(N))
+            c[0:1].fill_(S)
+            c[1:2].fill_(S + 1)
+            c[2:3].fill_(1)
+        eos, eos_first = set(eos_list), (eos_list[0] if eos_list else None)
+        return _PendingGeneration(eos_on_device=eos_on_device, st=st, skey=skey, B=R, Smax=Smax, V=V, out_tokens=out_tokens,
+                                  max_new_tokens=max_new_tokens, eos=eos, eos_first=eos_first, pad_token_id=pad_token_id,
+                                  return_logits=return_logits, all_logits=all_logits, forced_tokens=forced_tokens,
+                                  use_graph=use_graph, validate=validate, sync_every=sync_every, input_flags=self._input_flags, N=N)
 
     # ---- teacher-forced scoring ---------------------------------------------------------------------------------------
     XENT_CHUNK_ROWS = 8192          # scored rows per fused-head launch: partials workspace <= chunk x 16 KiB at V = 128256
@@ -1744,7 +1872,8 @@ class GARModel:
     def _decode_graph(self, st, B, Smax, out_tokens, skey):
         """(graph, logits buffer of the captured step). out_tokens is a [:, :n] slice of the state's [B, Smax] buffer:
         pointer and row stride depend on the state only, so one graph serves every max_new_tokens of the bucket."""
-        gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")), self.kv_cache_dtype)
+        gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")), self.kv_cache_dtype,
+                st["fan"]["Kp"].data_ptr() if st.get("fan") else 0)         # (the prompt caches live in another state)
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

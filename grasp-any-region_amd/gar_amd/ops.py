@@ -465,6 +465,30 @@ def attention_decode_workspace(B, Hq, hd, max_splits) -> int:
     return int(lib().gar_attention_decode_workspace(B, Hq, hd, max_splits))
 
 
+FANOUT_LAUNCHES = 0     # gar_attention_decode_fanout calls issued (captured ones count once): tests assert the shared kernel ran
+
+
+def attention_decode_fanout(qkv, cos, sin, Kp, Vp, Ksuf, Vsuf, O, B, N, Hq, Hkv, hd, Sp, T, prefix_len_dev, step_dev, q_scale,
+                            max_splits, workspace, left_pad=None, strip_order: bool = False):
+    """attention_decode_qkv for N continuations of each of B prompts: row b * N + i of ``qkv`` [B * N, (Hq + 2 Hkv) hd] attends over
+    prompt b's rows of ``Kp`` / ``Vp`` [B, Hkv, Sp, hd] (read once per kv head for up to 32 / G siblings) and its own rows of
+    ``Ksuf`` / ``Vsuf`` [B * N, Hkv, T, hd], to which the step's key / value are appended at row step_dev[0]. 16-bit only."""
+    global FANOUT_LAUNCHES
+    assert Kp.is_contiguous() and Vp.is_contiguous() and Ksuf.is_contiguous() and Vsuf.is_contiguous()
+    assert tuple(Kp.shape) == (B, Hkv, Sp, hd) and tuple(Ksuf.shape) == (B * N, Hkv, T, hd) and qkv.shape[0] == B * N
+    assert left_pad is None or (left_pad.dtype == torch.int32 and left_pad.numel() == B)
+    FANOUT_LAUNCHES += 1
+    _timed("attn_decode", 0.0, lambda: check(
+        lib(qkv.dtype).gar_attention_decode_fanout(dtype_code(qkv.dtype), ptr(qkv), ptr(cos), ptr(sin), ptr(Kp), ptr(Vp), ptr(Ksuf),
+                                                   ptr(Vsuf), ptr(O), B, N, Hq, Hkv, hd, Sp, T, ptr(prefix_len_dev), ptr(step_dev),
+                                                   ptr(left_pad), q_scale, int(strip_order), max_splits, ptr(workspace), stream()),
+        "gar_attention_decode_fanout"))
+
+
+def attention_decode_fanout_workspace(R, Hq, hd, max_splits) -> int:
+    return int(lib().gar_attention_decode_fanout_workspace(R, Hq, hd, max_splits))
+
+
 # ---- FP8 KV cache (include/gar_hip.h, ABI 16): Kc8 / Vc8 uint8 [B, Hkv, Smax, hd], Ks / Vs float32 [B, Hkv, Smax]
 def kv_quantize_fp8(K, V, Kc8, Vc8, Ks, Vs, B, Hkv, hd, Smax, S, kv_start: int = 0):
     """``K`` / ``V`` [B, Hkv, src_stride, hd] 16-bit -> rows kv_start .. S - 1 of the fp8 cache and its scale planes."""

@@ -270,6 +270,22 @@ int gar_attention_decode(int dtype, const void* q, int64_t q_stride, const void*
 int gar_attention_decode_qkv(int dtype, const void* qkv, const float* cos, const float* sin, void* Kc, void* Vc, void* O,
                              int B, int Hq, int Hkv, int hd, int Smax, const int32_t* pos_dev, const int32_t* left_pad,
                              float q_scale, int qk_strip_order, int max_splits, void* workspace, gar_stream_t stream);
+/* gar_attention_decode_qkv for N sampled continuations of each of B prompts (generate(num_return_sequences = N): HF expands the
+ * batch with repeat_interleave and runs the greedy step's attention of modeling_gar.py:418-426 on B*N full caches; here row
+ * r = b*N + i reads prompt b's rows ONCE per kv head for up to 32 / (Hq/Hkv) siblings — their query heads are the live MFMA
+ * columns — and its own generated rows). Kp, Vp [B,Hkv,Sp,hd]: the prompts' caches, rows left_pad[b] .. P-1 live, only read.
+ * Ksuf, Vsuf [B*N,Hkv,T,hd]: each row's generated tokens; the step appends the rotated key / the value at row t and attends over
+ * rows 0 .. t. `qkv` [B*N,(Hq+2Hkv)*hd] raw qkv GEMM output, RoPE position P - left_pad[b] + t, q_scale, qk_strip_order as in
+ * gar_attention_decode_qkv; P = prefix_len_dev[0] (clamped to 1 .. Sp), t = step_dev[0] (clamped to 0 .. T-1), device memory: one
+ * captured hipGraph replays for every token. O [B*N, Hq*hd]. The prefix splits (max_splits, 1..63, over B * Hkv * column blocks)
+ * and the suffix leave (m, l, O) partials of one softmax that gar_attention_decode's combine merges.
+ * workspace >= gar_attention_decode_fanout_workspace(B*N, ...) bytes. 16-bit only: GAR_ERR_UNSUPPORTED (nothing launched) for
+ * GAR_F32. Sp, T multiples of 64, head_dim 64 / 128. */
+int64_t gar_attention_decode_fanout_workspace(int R, int Hq, int hd, int max_splits);
+int gar_attention_decode_fanout(int dtype, const void* qkv, const float* cos, const float* sin, const void* Kp, const void* Vp,
+                                void* Ksuf, void* Vsuf, void* O, int B, int N, int Hq, int Hkv, int hd, int Sp, int T,
+                                const int32_t* prefix_len_dev, const int32_t* step_dev, const int32_t* left_pad, float q_scale,
+                                int qk_strip_order, int max_splits, void* workspace, gar_stream_t stream);
 
 /* ---- FP8 KV cache (ABI 16; GARModel(kv_cache_dtype="fp8")) ----------------------------------------------------------------
  * What these replace: HF's DynamicCache.update plus the attention of one greedy step (modeling_gar.py:418-426), with the cache
