@@ -11,6 +11,9 @@ def main():
     ap = base_parser("Inference demo of Grasp Any Region models (MI355X-native path).")
     ap.add_argument("--image_path", required=True)
     ap.add_argument("--mask_path", required=True)
+    ap.add_argument("--return_logprobs", action="store_true",
+                    help="print each caption's mean token log-probability; with --num_return_sequences N the captions come "
+                         "ordered by it, best first")
     args = ap.parse_args()
     model, processor, dtype = load(args)
     from evaluation.eval_dataset import SingleRegionCaptionDataset
@@ -22,7 +25,13 @@ def main():
                                          visual_prompt_tokens=prompt_tokens, data_dtype=dtype, device=args.device)
     data_sample = dataset[0]
     gc = generation_config(args, processor)
-    out = model.generate(**data_sample, generation_config=gc, return_dict=True, **sampling_kwargs(args, gc))
+    out = model.generate(**data_sample, generation_config=gc, return_dict=True, return_logprobs=args.return_logprobs,
+                         **sampling_kwargs(args, gc))
+    if args.return_logprobs:                # the model's own confidence in each caption: mean log-probability of its tokens
+        mean = (out.sum_logprobs / out.n_tokens.clamp(min=1)).tolist()
+        for r in sorted(range(len(mean)), key=lambda i: -mean[i]):
+            print(f"[{mean[r]:.4f}] " + processor.tokenizer.decode(out.sequences[r], skip_special_tokens=True).strip())
+        return
     for seq in out.sequences:               # one caption, or the --num_return_sequences sampled ones
         print(processor.tokenizer.decode(seq, skip_special_tokens=True).strip())
 

@@ -264,6 +264,88 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restric
     }
 }
 
+// argmax with the chosen token's log-probability (gar_argmax_lp): kernels of their own, so gar_argmax's two stay as they are.
+// Stage 1 is argmax_partial_kernel plus, per block, s = sum exp(x - block max) (a second pass over the block's ~V/64 logits, which
+// the first just pulled into the cache); stage 2 merges the 64 (max, s) pairs: sum_j s_j exp(m_j - M). The chosen token IS the
+// maximum, so log p = -log of that sum. Fixed-shape reductions throughout (xor tree in a wave, waves in order): deterministic.
+// An empty block (V < 64 x per) or one of -inf logits only holds (-inf, 0) and contributes 0, never exp(-inf - -inf) = NaN.
+template <typename T>
+__global__ __launch_bounds__(256) void argmax_lp_partial_kernel(const T* __restrict__ logits, int64_t ld, int V,
+                                                                float* __restrict__ pv, int* __restrict__ pi,
+                                                                float* __restrict__ ps) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ float ss[4];
+    const int b = blockIdx.y, blk = blockIdx.x;
+    const T* row = logits + (int64_t)b * ld;
+    const int per = (V + AM_BLOCKS - 1) / AM_BLOCKS;
+    const int lo = blk * per, hi = min(V, lo + per);
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lo + threadIdx.x; i < hi; i += 256) am_better(bv, bi, DT<T>::ld(row + i), i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        am_better(bv, bi, ov, oi);
+    }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    bv = sv[0];
+    bi = si[0];
+    for (int w = 1; w < 4; ++w) am_better(bv, bi, sv[w], si[w]);      // every thread: the block's (max, first index)
+    float s = 0.f;
+    if (bv > -INFINITY)
+        for (int i = lo + threadIdx.x; i < hi; i += 256) s += __expf(DT<T>::ld(row + i) - bv);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) ss[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        pv[b * AM_BLOCKS + blk] = bv;
+        pi[b * AM_BLOCKS + blk] = bi;
+        ps[b * AM_BLOCKS + blk] = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+    }
+}
+
+__global__ __launch_bounds__(64) void argmax_lp_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
+                                                             const float* __restrict__ ps, int64_t* __restrict__ out_tokens,
+                                                             int64_t out_stride, const int32_t* __restrict__ step_dev,
+                                                             int64_t* __restrict__ cur_tokens,
+                                                             const int64_t* __restrict__ eos_ids, int n_eos,
+                                                             int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
+                                                             float* __restrict__ lp_raw, float* __restrict__ lp_warped) {
+    const int b = blockIdx.x;
+    const float mv = pv[b * AM_BLOCKS + threadIdx.x];
+    float bv = mv;
+    int bi = pi[b * AM_BLOCKS + threadIdx.x];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        am_better(bv, bi, ov, oi);
+    }
+    float s = mv > -INFINITY ? ps[b * AM_BLOCKS + threadIdx.x] * __expf(mv - bv) : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x == 0) {
+        const int step = step_dev ? step_dev[0] : 0;
+        if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = bi;
+        if (cur_tokens) cur_tokens[b] = bi;
+        const float lp = 0.f - logf(s);             // x[tok] - max = 0: HF's processed scores of greedy search are the raw logits
+        if (lp_raw) lp_raw[(int64_t)b * out_stride + step] = lp;
+        if (lp_warped) lp_warped[(int64_t)b * out_stride + step] = lp;
+        if (finished && eos_ids && finished[b] < 0) {        // the stopping criterion, as in argmax_final_kernel
+            bool hit = false;
+            for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)bi);
+            if (hit) {
+                finished[b] = step;
+                if (done_count) atomicAdd(done_count, 1);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Sampling (do_sample = True): HF's warpers in their order — temperature, top-k, top-p — then one draw from what is left
 // (transformers TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper + torch.multinomial in GenerationMixin._sample;
@@ -303,14 +385,18 @@ __device__ __forceinline__ unsigned int philox_first(unsigned int c0, unsigned i
     return c0;
 }
 
-template <typename T>
+// LP (gar_sample_lp): the instantiation that also writes the drawn token's log-probabilities — raw = x[tok] - logsumexp(x[0:V]) over the
+// logits as stored, warped = z[tok] - max z - log Z2 over the kept set (the distribution the draw was taken from) — into planes laid
+// out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false compiles to what it was.
+template <typename T, bool LP>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V,
                                                              int64_t* __restrict__ out_tokens, int64_t out_stride,
                                                              const int32_t* __restrict__ step_dev, int64_t* __restrict__ cur_tokens,
                                                              const float* __restrict__ params, const int64_t* __restrict__ seed_dev,
                                                              const int64_t* __restrict__ eos_ids, int n_eos,
                                                              int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
-                                                             int row_offset) {
+                                                             int row_offset, float* __restrict__ lp_raw,
+                                                             float* __restrict__ lp_warped) {
     __shared__ float hist_f[SMP_WAVES][256];        // per-wave mass histograms (merged in wave order: deterministic)
     __shared__ int hist_i[256];
     __shared__ float red_f[SMP_WAVES];
@@ -343,6 +429,14 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
     mx = red_f[0];
     for (int w = 1; w < SMP_WAVES; ++w) mx = fmaxf(mx, red_f[w]);
     __syncthreads();
+    // ---- LP: the mass of the whole row at temperature 1, shifted by xs = max z * T (the row maximum up to one rounding)
+    const float xs = mx * temp;
+    float Zraw = 0.f;
+    if constexpr (LP) {
+        float praw = 0.f;
+        for (int i = tid; i < V; i += SMP_THREADS) praw += __expf(DT<T>::ld(row + i) - xs);
+        Zraw = block_sum(praw);
+    }
     // ---- top-k: the k-th largest key
     unsigned int key_lo = 0u;                       // keep key >= key_lo
     if (top_k > 0 && top_k < V) {
@@ -484,6 +578,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
         sh_u[1] = found ? 1u : 0u;
         sh_f[0] = run;
         sh_f[1] = target;
+        if constexpr (LP) sh_f[2] = Z2;
     }
     __syncthreads();
     if (tid == (int)sh_u[0] || (!sh_u[1] && tid == 0)) {
@@ -507,6 +602,10 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
         if (tok >= 0) {
             if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = tok;
             if (cur_tokens) cur_tokens[b] = tok;
+            if constexpr (LP) {                            // every exit above ends here with its tok: one place writes the planes
+                if (lp_raw) lp_raw[(int64_t)b * out_stride + step] = (DT<T>::ld(row + tok) - xs) - logf(Zraw);
+                if (lp_warped) lp_warped[(int64_t)b * out_stride + step] = (zof(tok) - mx) - logf(sh_f[2]);
+            }
             if (finished && eos_ids && finished[b] < 0) {
                 bool hit = false;
                 for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)tok);
@@ -527,11 +626,31 @@ extern "C" int gar_sample(int dtype, const void* logits, int64_t ld, int B, int 
     GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample: eos_ids / finished");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset);
+        hipLaunchKernelGGL((sample_kernel<bf16_t, false>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
+                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, (float*)nullptr,
+                           (float*)nullptr);
     else
-        hipLaunchKernelGGL((sample_kernel<float>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset);
+        hipLaunchKernelGGL((sample_kernel<float, false>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
+                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, (float*)nullptr,
+                           (float*)nullptr);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
+extern "C" int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                             const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
+                             const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
+                             float* lp_raw, float* lp_warped, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0, "sample_lp: bad args");
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample_lp: eos_ids / finished");
+    GAR_CHECK_ARG(lp_raw || lp_warped, "sample_lp: no log-probability plane (gar_sample is the form without)");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((sample_kernel<bf16_t, true>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
+                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+    else
+        hipLaunchKernelGGL((sample_kernel<float, true>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
+                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }
@@ -556,6 +675,33 @@ extern "C" int gar_argmax(int dtype, const void* logits, int64_t ld, int B, int 
         hipLaunchKernelGGL((argmax_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi);
     hipLaunchKernelGGL(argmax_final_kernel, dim3(B), dim3(64), 0, s, pv, pi, out_tokens, out_stride, step_dev, cur_tokens, eos_ids,
                        n_eos, finished, done_count);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
+extern "C" int64_t gar_argmax_lp_workspace(int B, int V) {
+    (void)V;
+    return (int64_t)B * AM_BLOCKS * 12;
+}
+
+extern "C" int gar_argmax_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
+                             int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace,
+                             const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, float* lp_raw,
+                             float* lp_warped, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0 && (out_tokens || cur_tokens), "argmax_lp: bad args");
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "argmax_lp: eos_ids / finished");
+    GAR_CHECK_ARG(lp_raw || lp_warped, "argmax_lp: no log-probability plane (gar_argmax is the form without)");
+    float* pv = (float*)workspace;
+    int* pi = (int*)(pv + (int64_t)B * AM_BLOCKS);
+    float* ps = pv + (int64_t)B * AM_BLOCKS * 2;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(AM_BLOCKS, B);
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((argmax_lp_partial_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)logits, ld, V, pv, pi, ps);
+    else
+        hipLaunchKernelGGL((argmax_lp_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi, ps);
+    hipLaunchKernelGGL(argmax_lp_final_kernel, dim3(B), dim3(64), 0, s, pv, pi, ps, out_tokens, out_stride, step_dev, cur_tokens,
+                       eos_ids, n_eos, finished, done_count, lp_raw, lp_warped);
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }

@@ -55,7 +55,11 @@ class ContinuousBatcher:
 
     def __init__(self, model, slots: int, max_new_tokens: int = 1024, eos_token_id=None, poll_every: int = 8,
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
-                 validate: bool = True, use_graph: bool = True, smax_multiple: int = 256):
+                 validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False):
+        if return_logprobs:
+            # generate(return_logprobs=True) writes planes laid out like the token matrix; this loop shifts that matrix (_rebase)
+            # and pop_finished returns token lists only: not threaded through here
+            raise hip.GarError("ContinuousBatcher: return_logprobs is not implemented (call generate(return_logprobs=True))")
         self.model, self.B = model, int(slots)
         model._check_decode_rows(self.B, "ContinuousBatcher slots")
         # every batcher owns its two KV-state slots (decode / staging) of the model: two batchers — or a batcher and a caller of
@@ -95,6 +99,8 @@ class ContinuousBatcher:
     def submit(self, sample: dict) -> int:
         if int(sample["input_ids"].shape[0]) != 1:
             raise ValueError("ContinuousBatcher.submit takes one region per sample (input_ids [1, S])")
+        if sample.get("return_logprobs"):
+            raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
         t = self._next_ticket
         self._next_ticket += 1
         self.queue.append((t, sample))

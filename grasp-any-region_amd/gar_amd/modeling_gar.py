@@ -48,6 +48,27 @@ class GenerateOutput:
     # GenerationPipeline only: event on the decode stream behind this output's last kernel — a consumer on another stream
     # (the caller's) waits for it before it reads ``sequences``
     done: Optional[object] = None
+    # return_logprobs=True only: the log-probability of every token of ``sequences``, written by the launch that
+    # chose it. A row counts up to and including its first eos; the columns behind it (``pad`` in ``sequences``) hold 0.
+    token_logprobs: Optional[torch.Tensor] = None           # f32 [B * N, n]: x[tok] - logsumexp(x) over the raw logits
+    token_logprobs_warped: Optional[torch.Tensor] = None    # f32 [B * N, n]: under the warped distribution the token was drawn
+    #                                                         from (temperature, top-k, top-p); greedy search: equal to the raw one
+    sum_logprobs: Optional[torch.Tensor] = None             # f32 [B * N]
+    sum_logprobs_warped: Optional[torch.Tensor] = None      # f32 [B * N]
+    n_tokens: Optional[torch.Tensor] = None                 # int32 [B * N]: counted tokens per row
+
+
+def logprob_outputs(raw: torch.Tensor, warped: torch.Tensor, finished_at: Sequence[Optional[int]]):
+    """The log-probability fields of a :class:`GenerateOutput` from the planes the decode steps wrote ([R, n] f32, one column
+    per step) and ``finished_at`` (per row: number of tokens up to and including its first eos, None = no eos among the n):
+    (token_logprobs, token_logprobs_warped, sum_logprobs, sum_logprobs_warped, n_tokens), 0 in the columns behind a row's eos
+    (ScoreOutput's "0 where ignored"). Torch ops on the planes' device; nothing is read back."""
+    R, n = raw.shape
+    ends = torch.tensor([n if f is None else min(int(f), n) for f in finished_at], dtype=torch.int64, device=raw.device)
+    keep = torch.arange(n, device=raw.device)[None, :] < ends[:, None]
+    zero = torch.zeros((), dtype=raw.dtype, device=raw.device)
+    raw, warped = torch.where(keep, raw, zero), torch.where(keep, warped, zero)
+    return raw, warped, raw.sum(1), warped.sum(1), ends.to(torch.int32)
 
 
 INPUT_COUNT_MISMATCH, INPUT_SPAN_LENGTH, INPUT_MISSING_BBOX, INPUT_ID_RANGE, INPUT_MASK_NOT_LEFT_PADDED = 1, 2, 4, 8, 16
@@ -1252,11 +1273,13 @@ class GARModel:
         return t
 
     def _head(self, last_rows: torch.Tensor, B: int, out_tokens, st, cur=None, normed: Optional[torch.Tensor] = None,
-              finished=None, row0: int = 0, decode: bool = False, pick: bool = True):
+              finished=None, row0: int = 0, decode: bool = False, pick: bool = True, lp=None):
         """final RMSNorm + lm_head + greedy argmax of the given [B, C] rows (row-strided view allowed). ``normed``: the
         rows after the final norm, when the caller's last launch produced them already (split-K decode path). ``decode``: a
         decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token. ``pick`` False:
-        the logits only — the caller draws the tokens (N draws per prompt row: _generate_begin_fanout)."""
+        the logits only — the caller draws the tokens (N draws per prompt row: _generate_begin_fanout). ``lp``: the (raw, warped)
+        log-probability planes of a return_logprobs request, sliced like ``out_tokens`` — the picking launch is then the one that
+        also writes the chosen token's log-probability (gar_argmax_lp / gar_sample_lp)."""
         gemm = self._gemm_w8 if decode and self.w_fp8 else ops.gemm
         cur = st["cur"] if cur is None else cur
         t = self.config.mllm_config.text_config
@@ -1276,12 +1299,16 @@ class GARModel:
         if not pick:
             return logits
         fin = st["finished"] if finished is None else finished
+        raw, warped = (None, None) if lp is None else lp
         if st.get("sampling"):
             ops.sample(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, st["sample_params"], st["sample_seed"],
-                       eos_ids=st["eos_ids"], finished=fin, done_count=st["done_count"], row_offset=row0)
+                       eos_ids=st["eos_ids"], finished=fin, done_count=st["done_count"], row_offset=row0, logprobs=raw,
+                       logprobs_warped=warped)
         else:
+            if lp is not None:      # one more f32 per partial block: a workspace of its own size
+                ws = self._buf(key, "amws_lp", (ops.argmax_lp_workspace(B, V),), torch.uint8)
             ops.argmax(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, ws, eos_ids=st["eos_ids"],
-                       finished=fin, done_count=st["done_count"])
+                       finished=fin, done_count=st["done_count"], logprobs=raw, logprobs_warped=warped)
         return logits
 
     def _decode_step(self, st, B: int, Smax: int, out_tokens):
@@ -1380,7 +1407,7 @@ class GARModel:
                     xn_ready = True
             else:
                 gemm(ff, ly["down"], h, hip.EPI_RES, residual=h)
-        logits = self._head(h, B, out_tokens, st, normed=normed, decode=True)
+        logits = self._head(h, B, out_tokens, st, normed=normed, decode=True, lp=st.get("lp"))
         ops.counter_add(st["counters"][0:3], 1)
         return logits
 
@@ -1502,7 +1529,8 @@ class GARModel:
                        max_new_tokens: Optional[int] = None, eos_token_id=None, use_graph: bool = True, validate: bool = True,
                        return_logits: bool = False, sync_every: int = 16, feature_replay_video: bool = False,
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
-                       state_slot: int = 0, seed: Optional[int] = None, **generate_kwargs) -> "_PendingGeneration":
+                       state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
+                       **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
         the request; None draws one from torch's global generator).
@@ -1513,7 +1541,12 @@ class GARModel:
 
         ``forced_tokens`` [B, n] (tests): teacher forcing — ``sequences`` / ``logits`` still report what the model chose at
         every step, but the token fed back as step j's input is ``forced_tokens[:, j]``, so two models (bf16 vs f32) can be
-        compared on identical contexts over a whole caption."""
+        compared on identical contexts over a whole caption.
+
+        ``return_logprobs``: the output carries the log-probability of every generated token (``token_logprobs`` under the raw
+        logits, ``token_logprobs_warped`` under the distribution a sampled token was drawn from, their per-row sums and
+        ``n_tokens``), written by the launch that picks the token — no dense logits leave the step. ``sequences`` are
+        bit for bit those of the call without it."""
         sampling = None
         N = 1
         get = _option_reader(generation_config, generate_kwargs)
@@ -1536,7 +1569,7 @@ class GARModel:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
                                                return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
-                                               state_slot)
+                                               state_slot, return_logprobs)
         # attention_mask is forwarded to the Llama generate by the reference (modeling_gar.py:418-426). A LEFT-padded batch
         # (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a
         # sequence keeps its rows in the padded layout, its RoPE positions count from its first real token and the padding
@@ -1549,6 +1582,7 @@ class GARModel:
         Smax = _round_up(S + max_new_tokens, 256)
         skey, st = self._llm_state(B, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (B, Smax), torch.int64, zero=True)[:, :max_new_tokens]
+        lp = st["lp"] = self._logprob_planes(skey, out_tokens, (B, Smax)) if return_logprobs else None
         eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
@@ -1559,7 +1593,8 @@ class GARModel:
         for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
                                                   feature_replay_video, video_frame_tokens):
             last = self._prefill(embeds, st, Smax, b0)
-            lg = self._head(last, b1 - b0, out_tokens[b0:b1], st, cur=st["cur"][b0:b1], finished=st["finished"][b0:b1], row0=b0)
+            lg = self._head(last, b1 - b0, out_tokens[b0:b1], st, cur=st["cur"][b0:b1], finished=st["finished"][b0:b1], row0=b0,
+                            lp=None if lp is None else (lp[0][b0:b1], lp[1][b0:b1]))
             if forced_tokens is not None:
                 st["cur"][b0:b1].copy_(forced_tokens[b0:b1, 0])
             if return_logits:
@@ -1579,6 +1614,12 @@ class GARModel:
                                   eos=eos, eos_first=eos_first, pad_token_id=pad_token_id, return_logits=return_logits,
                                   all_logits=all_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
                                   sync_every=sync_every, input_flags=self._input_flags, N=1)
+
+    def _logprob_planes(self, skey, out_tokens, shape):
+        """(raw, warped) f32 planes of a return_logprobs request: buffers of the state shaped like its token buffer and sliced
+        like ``out_tokens``, so (row stride, step column) address all three alike."""
+        return tuple(self._buf(skey, name, shape, torch.float32, zero=True)[:, :out_tokens.shape[1]]
+                     for name in ("lp_raw", "lp_warped"))
 
     def _arm_state(self, st, left_pad, eos_token_id, sampling, seed):
         """A state's request words before the prompt phase: counters, left_pad, the stopping criterion's latches and eos table, the
@@ -1612,7 +1653,8 @@ class GARModel:
 
     def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate, return_logits,
-                               sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot):
+                               sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot,
+                               return_logprobs=False):
         """generate_begin of a num_return_sequences = N > 1 request (do_sample): ONE prompt phase over the B prompts, N first
         tokens drawn from each prompt's logits, and a state of B * N rows for :meth:`generate_finish` — row b * N + i is sample i
         of prompt b, its draws counted by (seed, step, b * N + i) as the replicated batch's would be.
@@ -1639,6 +1681,7 @@ class GARModel:
             _, pst = self._llm_state(B, Smax, state_slot)
             skey, st = self._llm_state(R, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (R, Smax - Sp if shared else Smax), torch.int64, zero=True)[:, :max_new_tokens]
+        lp = st["lp"] = self._logprob_planes(skey, out_tokens, (R, Smax - Sp if shared else Smax)) if return_logprobs else None
         self._arm_state(pst, left_pad, None, None, None)
         eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed)
         first_logits = []
@@ -1653,7 +1696,8 @@ class GARModel:
             r0, r1 = _fanout_rows(b0, b1, N)
             ops.sample(lg, V, out_tokens[r0:r1], out_tokens.stride(0), st["counters"][2:3], st["cur"][r0:r1], st["sample_params"],
                        st["sample_seed"], eos_ids=st["eos_ids"], finished=st["finished"][r0:r1], done_count=st["done_count"],
-                       row_offset=r0)
+                       row_offset=r0, logprobs=None if lp is None else lp[0][r0:r1],
+                       logprobs_warped=None if lp is None else lp[1][r0:r1])
             if forced_tokens is not None:
                 st["cur"][r0:r1].copy_(forced_tokens[r0:r1, 0])
             if return_logits:
@@ -1850,8 +1894,15 @@ class GARModel:
                 cols = torch.arange(cut, device=self.device)[None, :]
                 ends = torch.tensor([(f if f is not None else cut) for f in finished_at], dtype=torch.int64, device=self.device)
                 seq = torch.where(cols < ends[:, None], seq[:, :cut], torch.full_like(seq[:, :cut], int(pad)))
+        lp_fields = {}
+        if st.get("lp") is not None:
+            # the planes hold the model's own choice of every step, as `sequences` does; behind a row's first eos — where
+            # `sequences` holds `pad` — they hold 0. Masks and sums: a few torch ops on the planes, nothing read back
+            raw, warped = (p[:, :seq.shape[1]] for p in st["lp"])
+            names = ("token_logprobs", "token_logprobs_warped", "sum_logprobs", "sum_logprobs_warped", "n_tokens")
+            lp_fields = dict(zip(names, logprob_outputs(raw, warped, finished_at if eos else [None] * B)))
         return GenerateOutput(sequences=seq, logits=torch.stack(all_logits, 1) if return_logits else None,
-                              input_flags=None if validate else self._input_flags)
+                              input_flags=None if validate else self._input_flags, **lp_fields)
 
     def _raise_on_input_flags(self):
         f = int(self._input_flags.item())
@@ -1873,7 +1924,8 @@ class GARModel:
         """(graph, logits buffer of the captured step). out_tokens is a [:, :n] slice of the state's [B, Smax] buffer:
         pointer and row stride depend on the state only, so one graph serves every max_new_tokens of the bucket."""
         gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")), self.kv_cache_dtype,
-                st["fan"]["Kp"].data_ptr() if st.get("fan") else 0)         # (the prompt caches live in another state)
+                st["fan"]["Kp"].data_ptr() if st.get("fan") else 0,         # (the prompt caches live in another state)
+                st.get("lp") is not None)                                   # return_logprobs: the step picks with the _lp launch
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

@@ -622,31 +622,57 @@ def embed_lookup(tokens, E, out):
                                  E.shape[0], stream()), "gar_embed_lookup")
 
 
-def argmax(logits, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids=None, finished=None, done_count=None):
+def _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
+    """the log-probability planes of :func:`argmax` / :func:`sample`: f32, laid out like ``out_tokens`` (same row stride)."""
+    for p in (logprobs, logprobs_warped):
+        assert p is None or (p.dtype == torch.float32 and out_tokens is not None and p.shape == out_tokens.shape
+                             and p.stride(0) == out_stride and p.stride(-1) == 1)
+    return logprobs is not None or logprobs_warped is not None
+
+
+def argmax(logits, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids=None, finished=None, done_count=None,
+           logprobs=None, logprobs_warped=None):
     """``eos_ids`` int64 [n] (device, entries < 0 never match), ``finished`` int32 [B] (-1 = running; the kernel latches the step
     at which a row first produced an eos id), ``done_count`` int32 [1] (number of latched rows): the greedy loop's stopping
-    criterion evaluated on the device (all optional)."""
+    criterion evaluated on the device (all optional). ``logprobs`` / ``logprobs_warped``: f32 planes shaped and strided like
+    ``out_tokens``; with either one the launch is ``gar_argmax_lp`` (``workspace`` >= :func:`argmax_lp_workspace` bytes), which
+    also writes the chosen token's log-probability at the step's column — equal in both planes for greedy search."""
     B = logits.shape[0]
     assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
     assert finished is None or (eos_ids is not None and finished.dtype == torch.int32 and finished.is_contiguous()
                                 and finished.numel() == B)
+    if _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
+        assert workspace.numel() * workspace.element_size() >= argmax_lp_workspace(B, V)
+        check(lib(logits.dtype).gar_argmax_lp(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens),
+                                              out_stride, ptr(step_dev), ptr(cur_tokens), ptr(workspace), ptr(eos_ids),
+                                              0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count),
+                                              ptr(logprobs), ptr(logprobs_warped), stream()), "gar_argmax_lp")
+        return
     check(lib(logits.dtype).gar_argmax(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
                            ptr(step_dev), ptr(cur_tokens), ptr(workspace), ptr(eos_ids),
                            0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count), stream()), "gar_argmax")
 
 
 def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed, eos_ids=None, finished=None, done_count=None,
-           row_offset: int = 0):
+           row_offset: int = 0, logprobs=None, logprobs_warped=None):
     """do_sample = True: temperature / top-k / top-p + one Philox draw per row (``gar_sample``). ``params`` float32 [3] (device):
     temperature, top_p, top_k; ``seed`` int64 [1] (device). Token placement and eos latches as :func:`argmax`. ``row_offset``: the
     batch row of ``logits[0]`` — the draw of row b is counted by (step, row_offset + b), so a batch whose first tokens come out of several
-    prompt chunks draws what the un-chunked batch draws (ABI 15)."""
+    prompt chunks draws what the un-chunked batch draws (ABI 15). ``logprobs`` / ``logprobs_warped``: f32 planes shaped and strided
+    like ``out_tokens``; with either one the launch is ``gar_sample_lp``, which also writes the drawn token's log-probability under
+    the raw logits / under the warped distribution it was drawn from."""
     B = logits.shape[0]
     assert params.dtype == torch.float32 and params.numel() >= 3 and params.is_contiguous()
     assert seed.dtype == torch.int64 and seed.numel() >= 1
     assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
     assert finished is None or (eos_ids is not None and finished.dtype == torch.int32 and finished.is_contiguous()
                                 and finished.numel() == B)
+    if _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
+        check(lib(logits.dtype).gar_sample_lp(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens),
+                                              out_stride, ptr(step_dev), ptr(cur_tokens), ptr(params), ptr(seed), ptr(eos_ids),
+                                              0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count),
+                                              int(row_offset), ptr(logprobs), ptr(logprobs_warped), stream()), "gar_sample_lp")
+        return
     check(lib(logits.dtype).gar_sample(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
                                        ptr(step_dev), ptr(cur_tokens), ptr(params), ptr(seed), ptr(eos_ids),
                                        0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count), int(row_offset),
@@ -656,6 +682,10 @@ def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed
 
 def argmax_workspace(B, V) -> int:
     return int(lib().gar_argmax_workspace(B, V))
+
+
+def argmax_lp_workspace(B, V) -> int:
+    return int(lib().gar_argmax_lp_workspace(B, V))
 
 
 def input_check(input_ids, vocab: int, counts, n_rows: int, spans, span_len: int, has_box, flags, attn_mask=None):

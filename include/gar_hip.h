@@ -493,6 +493,27 @@ int gar_sample(int dtype, const void* logits, int64_t ld, int B, int V, int64_t*
                const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
                const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset, gar_stream_t stream);
 
+/* ---- Log-probability of the token a step chose (GARModel.generate(return_logprobs=True)) ------------------------------------
+ * Additive: three new entry points, gar_argmax / gar_sample keep their signatures and their kernels, so GAR_ABI_VERSION stays 16.
+ * gar_argmax_lp / gar_sample_lp do what gar_argmax / gar_sample do — the token, cur_tokens and the eos latches are byte-identical
+ * on the same inputs — and, in the same launches, write f32 planes laid out like out_tokens (row stride out_stride, column
+ * step_dev[0]; either plane may be NULL, not both):
+ *   lp_raw     x[tok] - logsumexp(x[0:V]) over the logits as stored (the library's dtype read as f32; columns V..ld-1 are never
+ *              read): gar_xent_combine's definition, HF's compute_transition_scores(logits, normalize_logits=True);
+ *   lp_warped  the log-probability under the distribution the token was drawn from: z[tok] - max z - log Z2 with z = x / T over
+ *              the set top-k and top-p kept (HF: the same over `scores`); greedy search processes nothing, so there it equals lp_raw.
+ * The greedy form carries one more f32 per partial block (sum exp(x - block max)): workspace >= gar_argmax_lp_workspace() bytes.
+ * Reductions have a fixed shape, so the values are deterministic; -inf logits and empty partial blocks contribute 0, never NaN.
+ * No allocation, no synchronisation, hipGraph-capturable. */
+int gar_argmax_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                  const int32_t* step_dev, int64_t* cur_tokens, void* workspace, const int64_t* eos_ids, int n_eos,
+                  int32_t* finished, int32_t* done_count, float* lp_raw, float* lp_warped, gar_stream_t stream);
+int64_t gar_argmax_lp_workspace(int B, int V);
+int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                  const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
+                  const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset, float* lp_raw,
+                  float* lp_warped, gar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
