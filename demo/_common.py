@@ -37,6 +37,9 @@ def base_parser(description):
     ap.add_argument("--temperature", type=float, default=None, help="sampling temperature (implies sampling)")
     ap.add_argument("--top_p", type=float, default=None, help="nucleus sampling (implies sampling)")
     ap.add_argument("--top_k", type=int, default=None, help="top-k sampling (implies sampling)")
+    ap.add_argument("--top_logprobs", type=int, default=0, metavar="K",
+                    help="print, under each output and per generated token, the K most likely tokens as decoded-token:probability "
+                         "(raw softmax of the step's logits, also when sampling; K <= 32)")
     ap.add_argument("--synthetic_weights", action="store_true",
                     help="seeded random weights of the named size + the stub tokenizer (plumbing / benchmarking)")
     return ap
@@ -77,3 +80,14 @@ def generation_config(args, processor):
 def sampling_kwargs(args, gc):
     """generate() keywords that go with :func:`generation_config`: the request's Philox key when it samples"""
     return dict(seed=args.seed) if gc.get("do_sample") else {}
+
+
+def top_logprob_lines(out, row, tokenizer):
+    """--top_logprobs: one line per generated token of ``out.sequences[row]`` — the K alternatives of that step as
+    decoded-token:probability, best first. Stops at the row's first eos (ids -1 behind it)."""
+    lines = []
+    for ids, lps in zip(out.top_logprob_ids[row].tolist(), out.top_logprobs[row].exp().tolist()):
+        if ids[0] < 0:
+            break
+        lines.append("    " + "  ".join(f"{tokenizer.decode([i])!r}:{p:.4f}" for i, p in zip(ids, lps)))
+    return lines

@@ -4,7 +4,7 @@
 import numpy as np
 from PIL import Image
 
-from _common import base_parser, generation_config, load, sampling_kwargs
+from _common import base_parser, generation_config, load, sampling_kwargs, top_logprob_lines
 
 
 def main():
@@ -25,9 +25,12 @@ def main():
                                  device=args.device)
     data_sample = dataset[0]
     gc = generation_config(args, processor)
-    out = model.generate(**data_sample, generation_config=gc, return_dict=True, **sampling_kwargs(args, gc))
-    for seq in out.sequences:               # one answer, or the --num_return_sequences sampled ones
+    out = model.generate(**data_sample, generation_config=gc, return_dict=True, top_logprobs=args.top_logprobs,
+                         **sampling_kwargs(args, gc))
+    for r, seq in enumerate(out.sequences):     # one answer, or the --num_return_sequences sampled ones
         print(processor.tokenizer.decode(seq, skip_special_tokens=True).strip())
+        if args.top_logprobs:
+            print("\n".join(top_logprob_lines(out, r, processor.tokenizer)))
 
 
 if __name__ == "__main__":

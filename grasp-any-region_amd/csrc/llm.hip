@@ -5,6 +5,7 @@
 //   embed_lookup   embedding rows of the just-sampled tokens
 //   argmax         greedy sampling with first-index tie break; writes into the device-side token matrix
 //   sample         do_sample = True: temperature / top-k / top-p warpers + one Philox draw per row and step
+//   topk_lp        the k most likely tokens of a step and the log-probabilities of given token ids
 #include "common.h"
 
 // Column of natural dim d0 (first element of an 8-wide slice) inside a q / k head whose rows of W — and therefore whose columns
@@ -702,6 +703,245 @@ extern "C" int gar_argmax_lp(int dtype, const void* logits, int64_t ld, int B, i
         hipLaunchKernelGGL((argmax_lp_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi, ps);
     hipLaunchKernelGGL(argmax_lp_final_kernel, dim3(B), dim3(64), 0, s, pv, pi, ps, out_tokens, out_stride, step_dev, cur_tokens,
                        eos_ids, n_eos, finished, done_count, lp_raw, lp_warped);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// top-k / candidate log-probabilities of a step's logits (gar_topk_lp): lp[i] = x[i] - logsumexp(x[0:V]), the k largest entries in
+// the order (value descending, index ascending) — am_better's order, so entry 0 is gar_argmax's token — and lp at a fixed id list.
+// Both stages select by k rounds of block arg-max. Nothing is removed between rounds: round r takes the best element that comes
+// strictly AFTER round r-1's winner in that order (tk_after), so the elements stay untouched in registers (static indexing, no
+// scratch), ties and -inf logits keep their index order, and an exhausted block answers (-inf, TK_NONE) from then on.
+// Stage 1, grid (AM_BLOCKS, B): a block's ~V/64 logits in TK_ITEMS registers per thread (ITEMS = 0: V > 64 x 256 x TK_ITEMS, re-read
+// from the cache every round), its k best, and sum exp(x - block max) as argmax_lp_partial_kernel forms it. Stage 2, one block per
+// row: the 64 (max, sum) pairs merged as argmax_lp_final_kernel merges them, the 64 x k candidates selected the same way, the
+// candidate ids gathered from the row. Fixed-shape reductions (xor tree in a wave, waves in order), no atomics: deterministic.
+// ---------------------------------------------------------------------------------------------------------------
+#define TK_MAX 32
+#define TK_CAND_MAX 64
+#define TK_ITEMS 8
+#define TK_NONE 0x7fffffff
+
+__device__ __forceinline__ bool tk_after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
+
+// k rounds of block arg-max over what the 256 threads hold. local(pv, pi, v, i): the calling thread's best element strictly after
+// (pv, pi), (-inf, TK_NONE) when it has none left; emit(r, v, i): called by every thread with round r's winner. A thread's best
+// changes only when it held the last winner, and a wave's only when that thread is in it: every round one thread rescans its
+// elements and one wave redoes its xor tree; the other waves hand their standing best to the round's LDS slots. sv / si alternate
+// between two sets of 4 slots, so one barrier per round is enough (a set is rewritten two rounds later, behind the next barrier).
+template <typename Local, typename Emit>
+__device__ __forceinline__ void tk_select(int k, float (*sv)[4], int (*si)[4], Local local, Emit emit) {
+    const int wave = threadIdx.x >> 6;
+    float lv, wv;
+    int li, wi;
+    auto wave_best = [&]() {
+        wv = lv;
+        wi = li;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(wv, o, 64);
+            const int oi = __shfl_xor(wi, o, 64);
+            am_better(wv, wi, ov, oi);
+        }
+    };
+    local(INFINITY, -1, lv, li);
+    wave_best();
+    for (int r = 0; r < k; ++r) {
+        if ((threadIdx.x & 63) == 0) { sv[r & 1][wave] = wv; si[r & 1][wave] = wi; }
+        __syncthreads();
+        float bv = sv[r & 1][0];
+        int bi = si[r & 1][0], bw = 0;
+        for (int w = 1; w < 4; ++w) {
+            const float v = sv[r & 1][w];
+            const int i = si[r & 1][w];
+            if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; bw = w; }
+        }
+        emit(r, bv, bi);
+        if (bi == TK_NONE) {                    // fewer than k elements here (uniform: every thread holds the same bi)
+            for (++r; r < k; ++r) emit(r, -INFINITY, TK_NONE);
+            break;
+        }
+        if (bw == wave) {
+            if (li == bi) local(bv, bi, lv, li);
+            wave_best();
+        }
+    }
+}
+
+template <typename T, int ITEMS>
+__global__ __launch_bounds__(256) void topk_lp_partial_kernel(const T* __restrict__ logits, int64_t ld, int V, int k,
+                                                              float* __restrict__ cv, int* __restrict__ ci,
+                                                              float* __restrict__ ps) {
+    __shared__ float sv[2][4];
+    __shared__ int si[2][4];
+    __shared__ float ss[4];
+    __shared__ float rv[TK_MAX];                // the rounds' winners, stored together behind the loop
+    __shared__ int ri[TK_MAX];
+    const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+    const T* row = logits + (int64_t)b * ld;
+    const int per = (V + AM_BLOCKS - 1) / AM_BLOCKS;
+    const int lo = blk * per, hi = min(V, lo + per);
+    float x[ITEMS > 0 ? ITEMS : 1];
+    if constexpr (ITEMS > 0) {
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const int i = lo + tid + 256 * j;
+            x[j] = i < hi ? DT<T>::ld(row + i) : -INFINITY;
+        }
+    }
+    float* ov = cv + ((int64_t)b * AM_BLOCKS + blk) * k;
+    int* oi = ci + ((int64_t)b * AM_BLOCKS + blk) * k;
+    float m0 = -INFINITY;
+    tk_select(
+        k, sv, si,
+        [&](float pv, int pi, float& bv, int& bi) {
+            bv = -INFINITY;
+            bi = TK_NONE;
+            if constexpr (ITEMS > 0) {
+#pragma unroll
+                for (int j = 0; j < ITEMS; ++j) {
+                    const int i = lo + tid + 256 * j;
+                    if (i < hi && tk_after(x[j], i, pv, pi)) am_better(bv, bi, x[j], i);
+                }
+            } else {
+                for (int i = lo + tid; i < hi; i += 256) {
+                    const float v = DT<T>::ld(row + i);
+                    if (tk_after(v, i, pv, pi)) am_better(bv, bi, v, i);
+                }
+            }
+        },
+        [&](int r, float v, int i) {
+            if (r == 0) m0 = v;
+            if (tid == 0) { rv[r] = v; ri[r] = i; }
+        });
+    // sum exp(x - block max): argmax_lp_partial_kernel's sum, term for term (an empty or all -inf block: 0, never exp(-inf - -inf))
+    float s = 0.f;
+    if (m0 > -INFINITY) {
+        if constexpr (ITEMS > 0) {
+#pragma unroll
+            for (int j = 0; j < ITEMS; ++j)
+                if (lo + tid + 256 * j < hi) s += __expf(x[j] - m0);
+        } else {
+            for (int i = lo + tid; i < hi; i += 256) s += __expf(DT<T>::ld(row + i) - m0);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((tid & 63) == 0) ss[tid >> 6] = s;
+    __syncthreads();
+    if (tid < k) { ov[tid] = rv[tid]; oi[tid] = ri[tid]; }
+    if (tid == 0) ps[b * AM_BLOCKS + blk] = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+}
+
+// kw = the k of stage 1 (>= 1: the row maximum is its entry 0 also when only candidates are asked for), k = entries to write (0: none)
+template <typename T>
+__global__ __launch_bounds__(256) void topk_lp_final_kernel(const T* __restrict__ logits, int64_t ld, int V, int k, int kw,
+                                                            const float* __restrict__ cv, const int* __restrict__ ci,
+                                                            const float* __restrict__ ps, int32_t* __restrict__ top_ids,
+                                                            float* __restrict__ top_lp, int64_t top_row_stride,
+                                                            int64_t top_step_stride, const int32_t* __restrict__ cand_ids,
+                                                            int n_cand, float* __restrict__ cand_lp, int64_t cand_row_stride,
+                                                            int64_t cand_step_stride, const int32_t* __restrict__ step_dev) {
+    __shared__ float sv[2][4];
+    __shared__ int si[2][4];
+    __shared__ float sms[2];
+    __shared__ float rv[TK_MAX];
+    __shared__ int ri[TK_MAX];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int step = step_dev ? step_dev[0] : 0;
+    cv += (int64_t)b * AM_BLOCKS * kw;
+    ci += (int64_t)b * AM_BLOCKS * kw;
+    if (tid < 64) {                             // the row's (max, sum exp(x - max)) out of the 64 blocks': argmax_lp_final_kernel's merge
+        const float mv = cv[tid * kw];
+        float M = mv;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+        float s = mv > -INFINITY ? ps[b * AM_BLOCKS + tid] * __expf(mv - M) : 0.f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (tid == 0) { sms[0] = M; sms[1] = logf(s); }
+    }
+    __syncthreads();
+    const float M = sms[0], logS = sms[1];
+    if (k > 0) {
+        const int n = AM_BLOCKS * kw;           // <= 64 x 32 = 256 x TK_ITEMS
+        float x[TK_ITEMS];
+        int xi[TK_ITEMS];
+#pragma unroll
+        for (int j = 0; j < TK_ITEMS; ++j) {
+            const int e = tid + 256 * j;
+            x[j] = e < n ? cv[e] : -INFINITY;
+            xi[j] = e < n ? ci[e] : TK_NONE;
+        }
+        int32_t* oid = top_ids + (int64_t)b * top_row_stride + (int64_t)step * top_step_stride;
+        float* olp = top_lp + (int64_t)b * top_row_stride + (int64_t)step * top_step_stride;
+        tk_select(
+            k, sv, si,
+            [&](float pv, int pi, float& bv, int& bi) {
+                bv = -INFINITY;
+                bi = TK_NONE;
+#pragma unroll
+                for (int j = 0; j < TK_ITEMS; ++j)
+                    if (xi[j] != TK_NONE && tk_after(x[j], xi[j], pv, pi)) am_better(bv, bi, x[j], xi[j]);
+            },
+            [&](int r, float v, int i) {
+                if (tid == 0) { rv[r] = v; ri[r] = i; }
+            });
+        __syncthreads();
+        if (tid < k) {                          // k <= V: the row holds k elements, so every ri is one of them
+            oid[tid] = ri[tid];
+            olp[tid] = (rv[tid] - M) - logS;
+        }
+    }
+    if (cand_lp && tid < n_cand) {
+        const int id = cand_ids[tid];           // the caller checked the list; an id outside the row is not read
+        const float lp = (id >= 0 && id < V) ? (DT<T>::ld(logits + (int64_t)b * ld + id) - M) - logS : __builtin_nanf("");
+        cand_lp[(int64_t)b * cand_row_stride + (int64_t)step * cand_step_stride + tid] = lp;
+    }
+}
+
+extern "C" int64_t gar_topk_lp_workspace(int B, int V, int k) {
+    (void)V;
+    return (int64_t)B * AM_BLOCKS * (2 * (k > 1 ? k : 1) + 1) * 4;
+}
+
+extern "C" int gar_topk_lp(int dtype, const void* logits, int64_t ld, int B, int V, int k, int32_t* top_ids, float* top_lp,
+                           int64_t top_row_stride, int64_t top_step_stride, const int32_t* cand_ids, int n_cand, float* cand_lp,
+                           int64_t cand_row_stride, int64_t cand_step_stride, const int32_t* step_dev, void* workspace,
+                           gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0 && ld >= V, "topk_lp: bad args");
+    GAR_CHECK_ARG((top_ids != nullptr) == (top_lp != nullptr), "topk_lp: top_ids and top_lp go together");
+    GAR_CHECK_ARG(top_ids || cand_lp, "topk_lp: neither the top-k planes nor the candidate plane");
+    if (top_ids)
+        GAR_CHECK_ARG(k >= 1 && k <= TK_MAX && k <= V && top_step_stride >= k && top_row_stride >= top_step_stride,
+                      "topk_lp: k %d not in 1..min(%d, V = %d), or strides below k", k, TK_MAX, V);
+    else
+        GAR_CHECK_ARG(k == 0, "topk_lp: k %d without the top-k planes", k);
+    if (cand_lp)
+        GAR_CHECK_ARG(cand_ids && n_cand >= 1 && n_cand <= TK_CAND_MAX && cand_step_stride >= n_cand && cand_row_stride >= cand_step_stride,
+                      "topk_lp: %d candidates not in 1..%d, no id list, or strides below the count", n_cand, TK_CAND_MAX);
+    else
+        GAR_CHECK_ARG(n_cand == 0, "topk_lp: %d candidates without the candidate plane", n_cand);
+    const int kw = k > 1 ? k : 1;
+    float* cv = (float*)workspace;
+    int* ci = (int*)(cv + (int64_t)B * AM_BLOCKS * kw);
+    float* ps = cv + (int64_t)B * AM_BLOCKS * kw * 2;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(AM_BLOCKS, B);
+    const bool regs = (int64_t)V <= (int64_t)AM_BLOCKS * 256 * TK_ITEMS;
+#define LAUNCH_TK(TT)                                                                                                              \
+    do {                                                                                                                           \
+        if (regs)                                                                                                                  \
+            hipLaunchKernelGGL((topk_lp_partial_kernel<TT, TK_ITEMS>), grid, dim3(256), 0, s, (const TT*)logits, ld, V, kw, cv, ci, ps); \
+        else                                                                                                                       \
+            hipLaunchKernelGGL((topk_lp_partial_kernel<TT, 0>), grid, dim3(256), 0, s, (const TT*)logits, ld, V, kw, cv, ci, ps);  \
+        hipLaunchKernelGGL((topk_lp_final_kernel<TT>), dim3(B), dim3(256), 0, s, (const TT*)logits, ld, V, k, kw, cv, ci, ps,     \
+                           top_ids, top_lp, top_row_stride, top_step_stride, cand_ids, n_cand, cand_lp, cand_row_stride,           \
+                           cand_step_stride, step_dev);                                                                            \
+    } while (0)
+    if (dtype == GAR_BF16) LAUNCH_TK(bf16_t); else LAUNCH_TK(float);
+#undef LAUNCH_TK
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }

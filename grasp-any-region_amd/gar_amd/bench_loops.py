@@ -105,11 +105,15 @@ def hip_abi_version():
     return hip.ABI_VERSION
 
 
-def _generate(model, processor, sample, args, skip_special_tokens):
+def _generate(model, processor, sample, args, skip_special_tokens, candidate_token_ids=None):
+    """the decoded answer of one item; with ``candidate_token_ids`` (--option_logprobs) also the first step's log-probabilities
+    of those ids"""
+    extra = {} if candidate_token_ids is None else dict(candidate_token_ids=candidate_token_ids)
     out = model.generate(**sample, generation_config=dict(
         max_new_tokens=args.max_new_tokens, do_sample=False, eos_token_id=processor.tokenizer.eos_token_id,
-        pad_token_id=processor.tokenizer.pad_token_id), return_dict=True)
-    return processor.tokenizer.decode(out.sequences[0], skip_special_tokens=skip_special_tokens).strip()
+        pad_token_id=processor.tokenizer.pad_token_id), return_dict=True, **extra)
+    text = processor.tokenizer.decode(out.sequences[0], skip_special_tokens=skip_special_tokens).strip()
+    return text if candidate_token_ids is None else (text, out.candidate_logprobs[0, 0].tolist())
 
 
 class Batcher:
@@ -118,7 +122,9 @@ class Batcher:
     are run ``batch_size`` at a time as ONE ``generate`` — their prompts right-aligned in a left-padded ``input_ids``
     with the ``attention_mask`` the reference forwards to HF's generate (modeling_gar.py:418-426) — so the decode weight
     stream is shared by the whole batch instead of being paid per item. A row's text is cut at its own first EOS, which is
-    what a one-item call returns. ``generate_calls`` / ``items`` count what was run (tests)."""
+    what a one-item call returns. ``generate_calls`` / ``items`` count what was run (tests). An item added with
+    ``candidate_token_ids`` (--option_logprobs) is batched with items of the same id list — one list per ``generate`` — and its
+    ``finish`` also gets the first step's log-probabilities of those ids."""
 
     def __init__(self, model, processor, args, skip_special_tokens):
         self.model, self.processor, self.args, self.skip = model, processor, args, skip_special_tokens
@@ -128,30 +134,33 @@ class Batcher:
         self.generate_calls = 0
         self.items = 0
 
-    def add(self, idx, sample, finish):
+    def add(self, idx, sample, finish, candidate_token_ids=None):
         if self.bs == 1:
-            self._emit(idx, _generate(self.model, self.processor, sample, self.args, self.skip), finish)
+            got = _generate(self.model, self.processor, sample, self.args, self.skip, candidate_token_ids)
+            self._emit(idx, got, finish) if candidate_token_ids is None else self._emit(idx, got[0], finish, got[1])
             self.generate_calls += 1
             self.items += 1
             return
         key = (int(sample["pixel_values"].shape[0]), tuple(sample.get("video_frame_tokens") or ()),
                bool(sample.get("feature_replay_video")))
+        if candidate_token_ids is not None:
+            key += (tuple(candidate_token_ids),)
         g = self.groups.setdefault(key, [])
         g.append((idx, sample, finish))
         if len(g) >= self.bs:
-            self._run(self.groups.pop(key))
+            self._run(self.groups.pop(key), candidate_token_ids)
 
     def flush(self):
-        for key in list(self.groups):
-            self._run(self.groups.pop(key))
+        for key in list(self.groups):      # a key with a 4th entry carries its group's candidate id list
+            self._run(self.groups.pop(key), list(key[3]) if len(key) > 3 else None)
         print(f"[batcher] {self.items} items in {self.generate_calls} generate calls (batch_size {self.bs})", flush=True)
         return self.results
 
-    def _emit(self, idx, text, finish):
+    def _emit(self, idx, text, finish, *option_logprobs):
         print(text, flush=True)
-        self.results.append((idx, finish(text)))
+        self.results.append((idx, finish(text, *option_logprobs)))
 
-    def _run(self, group):
+    def _run(self, group, candidate_token_ids=None):
         tk = self.processor.tokenizer
         eos = tk.eos_token_id
         eos_set = set(eos) if isinstance(eos, (list, tuple)) else {eos}
@@ -174,13 +183,15 @@ class Batcher:
         if samples[0].get("feature_replay_video"):
             batch.update(feature_replay_video=True, video_frame_tokens=samples[0]["video_frame_tokens"])
         out = self.model.generate(**batch, generation_config=dict(
-            max_new_tokens=self.args.max_new_tokens, do_sample=False, eos_token_id=eos, pad_token_id=pad), return_dict=True)
+            max_new_tokens=self.args.max_new_tokens, do_sample=False, eos_token_id=eos, pad_token_id=pad), return_dict=True,
+            **({} if candidate_token_ids is None else dict(candidate_token_ids=candidate_token_ids)))
         self.generate_calls += 1
         self.items += len(samples)
         rows = out.sequences.tolist()
-        for (idx, _, finish), row in zip(group, rows):
+        first = None if candidate_token_ids is None else out.candidate_logprobs[:, 0].tolist()
+        for r, ((idx, _, finish), row) in enumerate(zip(group, rows)):
             cut = next((j + 1 for j, t in enumerate(row) if t in eos_set), len(row))     # its own EOS, inclusive
-            self._emit(idx, tk.decode(row[:cut], skip_special_tokens=self.skip).strip(), finish)
+            self._emit(idx, tk.decode(row[:cut], skip_special_tokens=self.skip).strip(), finish, *([] if first is None else [first[r]]))
 
 
 class ContinuousRunner:
@@ -252,12 +263,40 @@ def gar_bench_question(item, mode):
     raise NotImplementedError(mode)
 
 
-def run_gar_bench(argv=None):
-    from .eval_dataset import MultiRegionDataset
+def option_letters(item):
+    """the option letters of a GAR-Bench VQA item: the text before the first '.' of each ``choices`` entry ("A. <Prompt0>" -> "A")"""
+    return [str(op).split(".", 1)[0].strip() for op in item["choices"]]
+
+
+def option_token_ids(tokenizer, letters):
+    """one token id per option letter (encoded without special tokens); a letter that is not a single token stops the loop"""
+    ids = []
+    for letter in letters:
+        enc = tokenizer([letter], add_special_tokens=False)["input_ids"][0]
+        if len(enc) != 1:
+            raise ValueError(f"--option_logprobs: option letter {letter!r} encodes to {len(enc)} tokens {list(enc)}, not to one")
+        ids.append(int(enc[0]))
+    return ids
+
+
+def gar_bench_parser():
     ap = base_parser("Inference of Grasp Any Region models on GAR-Bench (MI355X-native path).", "HaochenWang/GAR-8B",
                      "gar_8b", "evaluation/GAR-Bench/annotations")
     ap.add_argument("--mode", choices=["vqa", "simple", "detailed"], required=True, help="mode to build questions")
-    args = ap.parse_args(argv)
+    ap.add_argument("--option_logprobs", action="store_true",
+                    help="--mode vqa: each record also gets option_logprobs — the log-probability of every option's letter as the "
+                         "FIRST generated token, in `choices` order (generate(candidate_token_ids=...)) — and option_pick, the letter "
+                         "of the largest; model_output and the accuracy print-out are unchanged. Not with --continuous")
+    return ap
+
+
+def run_gar_bench(argv=None):
+    from .eval_dataset import MultiRegionDataset
+    args = gar_bench_parser().parse_args(argv)
+    if args.option_logprobs and args.mode != "vqa":
+        raise SystemExit("--option_logprobs goes with --mode vqa (the items' `choices` name the option letters)")
+    if args.option_logprobs and args.continuous:
+        raise SystemExit("--option_logprobs is not implemented with --continuous (ContinuousBatcher returns token lists only)")
     model, processor, dtype, device, rank, world = load(args)
     data = json.load(open(args.anno_file))
     if args.limit:
@@ -266,11 +305,14 @@ def run_gar_bench(argv=None):
     prompt_tokens = [f"<Prompt{i}>" for i in range(prompt_number)] + ["<NO_Prompt>"]
     runner = make_runner(model, processor, args, skip_special_tokens=False)
 
-    def record(item):
-        def finish(text):
+    def record(item, letters=None):
+        def finish(text, option_logprobs=None):
             if text.endswith("<|eot_id|>"):
                 text = text.replace("<|eot_id|>", "")
-            return dict(item, model_output=text)
+            if option_logprobs is None:
+                return dict(item, model_output=text)
+            pick = letters[max(range(len(letters)), key=lambda c: option_logprobs[c])]
+            return dict(item, model_output=text, option_logprobs=option_logprobs, option_pick=pick)
         return finish
     for idx in dp.shard_indices(len(data), rank, world):
         item = data[idx]
@@ -279,7 +321,11 @@ def run_gar_bench(argv=None):
         ds = MultiRegionDataset(image=img, masks=masks, question_str=gar_bench_question(item, args.mode),
                                 processor=processor, prompt_number=prompt_number, visual_prompt_tokens=prompt_tokens,
                                 data_dtype=dtype, device=device)
-        runner.add(idx, ds[0], record(item))
+        if args.option_logprobs:
+            letters = option_letters(item)
+            runner.add(idx, ds[0], record(item, letters), candidate_token_ids=option_token_ids(processor.tokenizer, letters))
+        else:
+            runner.add(idx, ds[0], record(item))
     outputs = _gather(runner.flush(), rank, world)
     if outputs is None:
         return None

@@ -55,7 +55,13 @@ class ContinuousBatcher:
 
     def __init__(self, model, slots: int, max_new_tokens: int = 1024, eos_token_id=None, poll_every: int = 8,
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
-                 validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False):
+                 validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False,
+                 top_logprobs: int = 0, candidate_token_ids=None):
+        if top_logprobs or candidate_token_ids:
+            # generate()'s [rows, T, k] planes are addressed by the step's column like the token matrix this loop shifts (_rebase),
+            # and pop_finished returns token lists only: not threaded through here
+            raise hip.GarError("ContinuousBatcher: top_logprobs / candidate_token_ids are not implemented (call "
+                               "generate(top_logprobs=..., candidate_token_ids=...))")
         if return_logprobs:
             # generate(return_logprobs=True) writes planes laid out like the token matrix; this loop shifts that matrix (_rebase)
             # and pop_finished returns token lists only: not threaded through here
@@ -99,6 +105,9 @@ class ContinuousBatcher:
     def submit(self, sample: dict) -> int:
         if int(sample["input_ids"].shape[0]) != 1:
             raise ValueError("ContinuousBatcher.submit takes one region per sample (input_ids [1, S])")
+        if sample.get("top_logprobs") or sample.get("candidate_token_ids"):
+            raise hip.GarError("ContinuousBatcher.submit: top_logprobs / candidate_token_ids are not implemented (call "
+                               "generate(top_logprobs=..., candidate_token_ids=...))")
         if sample.get("return_logprobs"):
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
         t = self._next_ticket

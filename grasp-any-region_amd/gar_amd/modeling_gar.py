@@ -56,6 +56,12 @@ class GenerateOutput:
     sum_logprobs: Optional[torch.Tensor] = None             # f32 [B * N]
     sum_logprobs_warped: Optional[torch.Tensor] = None      # f32 [B * N]
     n_tokens: Optional[torch.Tensor] = None                 # int32 [B * N]: counted tokens per row
+    # top_logprobs=k / candidate_token_ids=[...] only: RAW log-probabilities x[i] - logsumexp(x) of every step's logits,
+    # also under do_sample. Columns behind a row's first eos hold id -1 and value 0.0.
+    top_logprob_ids: Optional[torch.Tensor] = None          # int64 [B * N, n, k]: the k most likely tokens, best first, equal logits
+    #                                                         by ascending id — entry 0 is the greedy token
+    top_logprobs: Optional[torch.Tensor] = None             # f32 [B * N, n, k]: their log-probabilities
+    candidate_logprobs: Optional[torch.Tensor] = None       # f32 [B * N, n, C]: log-probabilities of candidate_token_ids, in their order
 
 
 def logprob_outputs(raw: torch.Tensor, warped: torch.Tensor, finished_at: Sequence[Optional[int]]):
@@ -69,6 +75,36 @@ def logprob_outputs(raw: torch.Tensor, warped: torch.Tensor, finished_at: Sequen
     zero = torch.zeros((), dtype=raw.dtype, device=raw.device)
     raw, warped = torch.where(keep, raw, zero), torch.where(keep, warped, zero)
     return raw, warped, raw.sum(1), warped.sum(1), ends.to(torch.int32)
+
+
+def top_logprob_options(top_logprobs, candidate_token_ids, V: int):
+    """(k, candidate id list) of a generate(top_logprobs=, candidate_token_ids=) request, checked against the vocabulary size and
+    gar_topk_lp's limits. ValueError names what is refused."""
+    k = top_logprobs
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= min(ops.TOPK_MAX, V):
+        raise ValueError(f"top_logprobs={k!r}: an int in 0..{min(ops.TOPK_MAX, V)} (min({ops.TOPK_MAX}, vocab_size = {V}))")
+    cands = [] if candidate_token_ids is None else list(candidate_token_ids)
+    if len(cands) > ops.TOPK_CAND_MAX:
+        raise ValueError(f"candidate_token_ids: {len(cands)} ids, at most {ops.TOPK_CAND_MAX}")
+    for c in cands:
+        if isinstance(c, bool) or int(c) != c or not 0 <= int(c) < V:
+            raise ValueError(f"candidate_token_ids: id {c!r} is outside [0, vocab_size = {V})")
+    return k, [int(c) for c in cands]
+
+
+def top_logprob_outputs(tk, n: int, finished_at: Sequence[Optional[int]]):
+    """The top_logprob_ids / top_logprobs / candidate_logprobs fields from a state's planes ([R, T, k] / [R, T, C], one column per
+    step), masked as :func:`logprob_outputs` masks: behind a row's first eos ids are -1 and values 0.0."""
+    dev = tk["cand_lp"].device if tk["ids"] is None else tk["ids"].device
+    ends = torch.tensor([n if f is None else min(int(f), n) for f in finished_at], dtype=torch.int64, device=dev)
+    keep = (torch.arange(n, device=dev)[None, :] < ends[:, None])[:, :, None]
+    out = {}
+    if tk["ids"] is not None:
+        out["top_logprob_ids"] = torch.where(keep, tk["ids"][:, :n].to(torch.int64), torch.full((), -1, dtype=torch.int64, device=dev))
+        out["top_logprobs"] = torch.where(keep, tk["lp"][:, :n], torch.zeros((), dtype=torch.float32, device=dev))
+    if tk["cand_lp"] is not None:
+        out["candidate_logprobs"] = torch.where(keep, tk["cand_lp"][:, :n], torch.zeros((), dtype=torch.float32, device=dev))
+    return out
 
 
 INPUT_COUNT_MISMATCH, INPUT_SPAN_LENGTH, INPUT_MISSING_BBOX, INPUT_ID_RANGE, INPUT_MASK_NOT_LEFT_PADDED = 1, 2, 4, 8, 16
@@ -1273,13 +1309,14 @@ class GARModel:
         return t
 
     def _head(self, last_rows: torch.Tensor, B: int, out_tokens, st, cur=None, normed: Optional[torch.Tensor] = None,
-              finished=None, row0: int = 0, decode: bool = False, pick: bool = True, lp=None):
+              finished=None, row0: int = 0, decode: bool = False, pick: bool = True, lp=None, tk=None):
         """final RMSNorm + lm_head + greedy argmax of the given [B, C] rows (row-strided view allowed). ``normed``: the
         rows after the final norm, when the caller's last launch produced them already (split-K decode path). ``decode``: a
         decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token. ``pick`` False:
         the logits only — the caller draws the tokens (N draws per prompt row: _generate_begin_fanout). ``lp``: the (raw, warped)
         log-probability planes of a return_logprobs request, sliced like ``out_tokens`` — the picking launch is then the one that
-        also writes the chosen token's log-probability (gar_argmax_lp / gar_sample_lp)."""
+        also writes the chosen token's log-probability (gar_argmax_lp / gar_sample_lp). ``tk``: the planes of a top_logprobs /
+        candidate_token_ids request for these rows (:meth:`_topk_planes`) — one gar_topk_lp beside the pick; it reads the logits only."""
         gemm = self._gemm_w8 if decode and self.w_fp8 else ops.gemm
         cur = st["cur"] if cur is None else cur
         t = self.config.mllm_config.text_config
@@ -1296,6 +1333,8 @@ class GARModel:
         else:
             ops.rmsnorm(last_rows, self.final_norm, t.rms_norm_eps, out=xn)
             gemm(xn, self.lm_head, logits)
+        if tk is not None:
+            self._topk_launch(logits, V, st, tk, key)
         if not pick:
             return logits
         fin = st["finished"] if finished is None else finished
@@ -1310,6 +1349,39 @@ class GARModel:
             ops.argmax(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, ws, eos_ids=st["eos_ids"],
                        finished=fin, done_count=st["done_count"], logprobs=raw, logprobs_warped=warped)
         return logits
+
+    def _topk_planes(self, skey, st, shape, k: int, cands):
+        """st["tk"] of a request: None without top_logprobs / candidate_token_ids, else the planes gar_topk_lp writes — buffers of the
+        state named by (k, C), [rows, T, k] / [rows, T, C] with T the state's token capacity, so their pointers are the captured
+        step's as long as the state lives — and the candidate ids, uploaded once per request."""
+        if not k and not cands:
+            st["tk"] = None
+            return None
+        R, T = shape
+        C_ = len(cands)
+        tk = dict(k=k, C=C_, ids=None, lp=None, cand_ids=None, cand_lp=None)
+        if k:
+            tk["ids"] = self._buf(skey, f"top_ids{k}", (R, T, k), torch.int32, zero=True)
+            tk["lp"] = self._buf(skey, f"top_lp{k}", (R, T, k), torch.float32, zero=True)
+        if C_:
+            tk["cand_ids"] = self._buf(skey, f"cand_ids{C_}", (C_,), torch.int32, zero=True)
+            tk["cand_ids"].copy_(self._upload(cands, torch.int32))
+            tk["cand_lp"] = self._buf(skey, f"cand_lp{C_}", (R, T, C_), torch.float32, zero=True)
+        st["tk"] = tk
+        return tk
+
+    @staticmethod
+    def _topk_rows(tk, r0: int, r1: int):
+        """``tk`` with its planes cut to rows r0 .. r1 - 1 (a prompt chunk's first-token head), as ``out_tokens[b0:b1]`` is"""
+        if tk is None:
+            return None
+        return dict(tk, **{n: tk[n][r0:r1] for n in ("ids", "lp", "cand_lp") if tk[n] is not None})
+
+    def _topk_launch(self, logits, V, st, tk, key):
+        B = logits.shape[0]
+        ws = self._buf(key, f"tkws{tk['k']}", (ops.topk_lp_workspace(B, V, tk["k"]),), torch.uint8)   # by k: a captured step keeps its own
+        ops.topk_lp(logits, V, st["counters"][2:3], ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"],
+                    cand_lp=tk["cand_lp"])
 
     def _decode_step(self, st, B: int, Smax: int, out_tokens):
         t = self.config.mllm_config.text_config
@@ -1407,7 +1479,7 @@ class GARModel:
                     xn_ready = True
             else:
                 gemm(ff, ly["down"], h, hip.EPI_RES, residual=h)
-        logits = self._head(h, B, out_tokens, st, normed=normed, decode=True, lp=st.get("lp"))
+        logits = self._head(h, B, out_tokens, st, normed=normed, decode=True, lp=st.get("lp"), tk=st.get("tk"))
         ops.counter_add(st["counters"][0:3], 1)
         return logits
 
@@ -1530,6 +1602,7 @@ class GARModel:
                        return_logits: bool = False, sync_every: int = 16, feature_replay_video: bool = False,
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
+                       top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None,
                        **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
@@ -1546,7 +1619,15 @@ class GARModel:
         ``return_logprobs``: the output carries the log-probability of every generated token (``token_logprobs`` under the raw
         logits, ``token_logprobs_warped`` under the distribution a sampled token was drawn from, their per-row sums and
         ``n_tokens``), written by the launch that picks the token — no dense logits leave the step. ``sequences`` are
-        bit for bit those of the call without it."""
+        bit for bit those of the call without it.
+
+        ``top_logprobs`` = k (0..min(32, vocab)) / ``candidate_token_ids`` (at most 64 ids in [0, vocab)): per generated token the
+        k most likely tokens with their log-probabilities (``top_logprob_ids`` / ``top_logprobs`` [B * N, n, k], best first, equal
+        logits by ascending id) and the log-probabilities of the given ids (``candidate_logprobs`` [B * N, n, C]). The
+        values are always RAW log-probabilities x[i] - logsumexp(x) of the step's logits, also with ``do_sample=True`` — the warped
+        value of the drawn token stays ``token_logprobs_warped``. Columns behind a row's first eos hold id -1 / value 0.0; with
+        ``forced_tokens`` the fields describe the model's own distribution. Independent of ``return_logprobs``; tokens unchanged."""
+        top_k_lp, cands = top_logprob_options(top_logprobs, candidate_token_ids, self.config.mllm_config.text_config.vocab_size)
         sampling = None
         N = 1
         get = _option_reader(generation_config, generate_kwargs)
@@ -1569,7 +1650,7 @@ class GARModel:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
                                                return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
-                                               state_slot, return_logprobs)
+                                               state_slot, return_logprobs, top_k_lp, cands)
         # attention_mask is forwarded to the Llama generate by the reference (modeling_gar.py:418-426). A LEFT-padded batch
         # (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a
         # sequence keeps its rows in the padded layout, its RoPE positions count from its first real token and the padding
@@ -1583,6 +1664,7 @@ class GARModel:
         skey, st = self._llm_state(B, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (B, Smax), torch.int64, zero=True)[:, :max_new_tokens]
         lp = st["lp"] = self._logprob_planes(skey, out_tokens, (B, Smax)) if return_logprobs else None
+        tk = self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
         eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
@@ -1594,7 +1676,7 @@ class GARModel:
                                                   feature_replay_video, video_frame_tokens):
             last = self._prefill(embeds, st, Smax, b0)
             lg = self._head(last, b1 - b0, out_tokens[b0:b1], st, cur=st["cur"][b0:b1], finished=st["finished"][b0:b1], row0=b0,
-                            lp=None if lp is None else (lp[0][b0:b1], lp[1][b0:b1]))
+                            lp=None if lp is None else (lp[0][b0:b1], lp[1][b0:b1]), tk=self._topk_rows(tk, b0, b1))
             if forced_tokens is not None:
                 st["cur"][b0:b1].copy_(forced_tokens[b0:b1, 0])
             if return_logits:
@@ -1654,7 +1736,7 @@ class GARModel:
     def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate, return_logits,
                                sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot,
-                               return_logprobs=False):
+                               return_logprobs=False, top_k_lp=0, cands=()):
         """generate_begin of a num_return_sequences = N > 1 request (do_sample): ONE prompt phase over the B prompts, N first
         tokens drawn from each prompt's logits, and a state of B * N rows for :meth:`generate_finish` — row b * N + i is sample i
         of prompt b, its draws counted by (seed, step, b * N + i) as the replicated batch's would be.
@@ -1682,6 +1764,7 @@ class GARModel:
             skey, st = self._llm_state(R, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (R, Smax - Sp if shared else Smax), torch.int64, zero=True)[:, :max_new_tokens]
         lp = st["lp"] = self._logprob_planes(skey, out_tokens, (R, Smax - Sp if shared else Smax)) if return_logprobs else None
+        tk = self._topk_planes(skey, st, (R, Smax - Sp if shared else Smax), top_k_lp, list(cands))
         self._arm_state(pst, left_pad, None, None, None)
         eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed)
         first_logits = []
@@ -1694,6 +1777,8 @@ class GARModel:
             last = self._prefill(embeds, pst, Sp, b0)
             lg = self._head(last, b1 - b0, None, pst, pick=False).repeat_interleave(N, 0)      # the SAME logits for the N draws
             r0, r1 = _fanout_rows(b0, b1, N)
+            if tk is not None:          # the N rows of a prompt carry that prompt's values at step 0
+                self._topk_launch(lg, V, st, self._topk_rows(tk, r0, r1), ("head", r1 - r0, st.get("slot", 0)))
             ops.sample(lg, V, out_tokens[r0:r1], out_tokens.stride(0), st["counters"][2:3], st["cur"][r0:r1], st["sample_params"],
                        st["sample_seed"], eos_ids=st["eos_ids"], finished=st["finished"][r0:r1], done_count=st["done_count"],
                        row_offset=r0, logprobs=None if lp is None else lp[0][r0:r1],
@@ -1901,6 +1986,8 @@ class GARModel:
             raw, warped = (p[:, :seq.shape[1]] for p in st["lp"])
             names = ("token_logprobs", "token_logprobs_warped", "sum_logprobs", "sum_logprobs_warped", "n_tokens")
             lp_fields = dict(zip(names, logprob_outputs(raw, warped, finished_at if eos else [None] * B)))
+        if st.get("tk") is not None:
+            lp_fields.update(top_logprob_outputs(st["tk"], seq.shape[1], finished_at if eos else [None] * B))
         return GenerateOutput(sequences=seq, logits=torch.stack(all_logits, 1) if return_logits else None,
                               input_flags=None if validate else self._input_flags, **lp_fields)
 
@@ -1925,7 +2012,8 @@ class GARModel:
         pointer and row stride depend on the state only, so one graph serves every max_new_tokens of the bucket."""
         gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")), self.kv_cache_dtype,
                 st["fan"]["Kp"].data_ptr() if st.get("fan") else 0,         # (the prompt caches live in another state)
-                st.get("lp") is not None)                                   # return_logprobs: the step picks with the _lp launch
+                st.get("lp") is not None,                                   # return_logprobs: the step picks with the _lp launch
+                (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0))  # top_logprobs / candidates: one more launch, planes by (k, C)
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

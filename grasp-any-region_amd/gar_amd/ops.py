@@ -688,6 +688,39 @@ def argmax_lp_workspace(B, V) -> int:
     return int(lib().gar_argmax_lp_workspace(B, V))
 
 
+TOPK_MAX, TOPK_CAND_MAX = 32, 64     # gar_topk_lp: largest k, longest candidate list
+
+
+def topk_lp_workspace(B, V, k) -> int:
+    return int(lib().gar_topk_lp_workspace(B, V, k))
+
+
+def topk_lp(logits, V, step_dev, workspace, top_ids=None, top_lp=None, cand_ids=None, cand_lp=None):
+    """``gar_topk_lp`` on the rows of ``logits`` [B, ld], with lp[i] = x[i] - logsumexp(x[0:V]): the k largest entries (value
+    descending, equal values by ascending index — entry 0 is :func:`argmax`'s token) into ``top_ids`` int32 / ``top_lp`` f32
+    [B, T, k] at column ``step_dev[0]`` (row-strided views allowed; 1 <= k <= min(32, V)), and lp at the ids of ``cand_ids``
+    (device int32 [C], C <= 64, shared by the rows; the caller has checked them against V) into ``cand_lp`` f32 [B, T, C]. Either
+    group may be absent, not both. ``workspace`` >= :func:`topk_lp_workspace` bytes."""
+    B = logits.shape[0]
+    k = C_ = 0
+    trs = tss = crs = css = 0
+    if (top_ids is None) != (top_lp is None) or (cand_ids is None) != (cand_lp is None):
+        raise hip.GarError("topk_lp: top_ids goes with top_lp, cand_ids with cand_lp")
+    if top_ids is not None:
+        assert top_ids.dtype == torch.int32 and top_lp.dtype == torch.float32 and top_ids.dim() == 3 and top_ids.shape[0] == B
+        assert top_ids.shape == top_lp.shape and top_ids.stride() == top_lp.stride() and top_ids.stride(2) == 1
+        k, trs, tss = top_ids.shape[2], top_ids.stride(0), top_ids.stride(1)
+    if cand_lp is not None:
+        assert cand_ids.dtype == torch.int32 and cand_ids.dim() == 1 and cand_ids.is_contiguous()
+        assert cand_lp.dtype == torch.float32 and cand_lp.dim() == 3 and cand_lp.shape[0] == B and cand_lp.stride(2) == 1
+        assert cand_lp.shape[2] == cand_ids.numel()
+        C_, crs, css = cand_ids.numel(), cand_lp.stride(0), cand_lp.stride(1)
+    assert workspace.numel() * workspace.element_size() >= topk_lp_workspace(B, V, k)
+    check(lib(logits.dtype).gar_topk_lp(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, k, ptr(top_ids), ptr(top_lp),
+                                        trs, tss, ptr(cand_ids), C_, ptr(cand_lp), crs, css, ptr(step_dev), ptr(workspace),
+                                        stream()), "gar_topk_lp")
+
+
 def input_check(input_ids, vocab: int, counts, n_rows: int, spans, span_len: int, has_box, flags, attn_mask=None):
     """device-side input checks of generate(validate=False): ORs INPUT_* bits into ``flags`` (int32 [1]). ``attn_mask``: bool /
     uint8 [B, S] generation mask; a row that is not left-padded sets INPUT_MASK_NOT_LEFT_PADDED."""

@@ -514,6 +514,25 @@ int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64
                   const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset, float* lp_raw,
                   float* lp_warped, gar_stream_t stream);
 
+/* ---- Top-k and candidate-token log-probabilities of a step (GARModel.generate(top_logprobs=k, candidate_token_ids=[...])) -----
+ * Additive: two new entry points, GAR_ABI_VERSION stays 16. Per row b of logits [B, ld] (the library's dtype read as f32; columns
+ * V..ld-1 are never read), with lp[i] = x[i] - logsumexp(x[0:V]) — gar_argmax_lp's / gar_xent_combine's raw definition:
+ *   top-k       1 <= k <= min(32, V): the k largest logits in the order (value descending, index ascending) — gar_argmax's tie rule,
+ *               so entry 0 is gar_argmax's token (its value is gar_argmax_lp's lp_raw, formed the same way). Entry r goes to
+ *               top_ids / top_lp [b * top_row_stride + step_dev[0] * top_step_stride + r] (int32 / f32 planes [rows, T, k] of their
+ *               own layout; step_dev NULL = step 0). top_ids and top_lp go together; without them k = 0.
+ *   candidates  1 <= n_cand <= 64: cand_lp[b * cand_row_stride + step * cand_step_stride + c] = lp[cand_ids[c]] for one device int32
+ *               list shared by all rows. The caller checks the ids (GARModel refuses ids outside [0, V) on the host); the kernel
+ *               does not read outside the row and writes NaN for such an id. Without cand_lp n_cand = 0.
+ * Either group may be absent, not both. -inf logits have lp = -inf and sort last, by index; empty and all -inf partial blocks
+ * contribute 0 to the sum, never NaN; NaN logits are unspecified. Two launches (64 partial blocks per row, then one block per row);
+ * reductions of fixed shape and no atomics, so values and order are deterministic. workspace >= gar_topk_lp_workspace() bytes.
+ * No allocation, no synchronisation, hipGraph-capturable. */
+int gar_topk_lp(int dtype, const void* logits, int64_t ld, int B, int V, int k, int32_t* top_ids, float* top_lp,
+                int64_t top_row_stride, int64_t top_step_stride, const int32_t* cand_ids, int n_cand, float* cand_lp,
+                int64_t cand_row_stride, int64_t cand_step_stride, const int32_t* step_dev, void* workspace, gar_stream_t stream);
+int64_t gar_topk_lp_workspace(int B, int V, int k);
+
 #ifdef __cplusplus
 }
 #endif
