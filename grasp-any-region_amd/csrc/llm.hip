@@ -5,6 +5,8 @@
 //   embed_lookup   embedding rows of the just-sampled tokens
 //   argmax         greedy sampling with first-index tie break; writes into the device-side token matrix
 //   sample         do_sample = True: temperature / top-k / top-p warpers + one Philox draw per row and step
+//                  (both with an LP instantiation that also writes the chosen token's log-probability;
+//                  one epilogue, commit_token, commits the token)
 //   topk_lp        the k most likely tokens of a step and the log-probabilities of given token ids
 #include "common.h"
 
@@ -197,7 +199,9 @@ extern "C" int gar_embed_lookup(int dtype, const int64_t* tokens, const void* E,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// argmax: stage 1 = AM_BLOCKS partial (max, first index) per row; stage 2 = one wave per row.
+// Token pick. What the greedy kernels, sample_kernel and the topk_lp kernels share is written once here: the order of (value, index)
+// pairs and its wave reduction (beside common.h's wave_sum / wave_max), the two halves of logsumexp over AM_BLOCKS blocks, and the
+// epilogue that commits a row's token. Every reduction has a fixed shape (xor tree inside a wave, waves in order): deterministic.
 // ---------------------------------------------------------------------------------------------------------------
 #define AM_BLOCKS 64
 
@@ -205,75 +209,67 @@ __device__ __forceinline__ void am_better(float& bv, int& bi, float v, int i) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict__ logits, int64_t ld, int V,
-                                                             float* __restrict__ pv, int* __restrict__ pi) {
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    const int b = blockIdx.y, blk = blockIdx.x;
-    const T* row = logits + (int64_t)b * ld;
-    const int per = (V + AM_BLOCKS - 1) / AM_BLOCKS;
-    const int lo = blk * per, hi = min(V, lo + per);
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = lo + threadIdx.x; i < hi; i += 256) am_better(bv, bi, DT<T>::ld(row + i), i);
+__device__ __forceinline__ void wave_best(float& bv, int& bi) {         // every lane: the wave's best pair in am_better's order
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(bv, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
         am_better(bv, bi, ov, oi);
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) am_better(bv, bi, sv[w], si[w]);
-        pv[b * AM_BLOCKS + blk] = bv;
-        pi[b * AM_BLOCKS + blk] = bi;
     }
 }
 
-__global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
-                                                          int64_t* __restrict__ out_tokens, int64_t out_stride,
-                                                          const int32_t* __restrict__ step_dev,
-                                                          int64_t* __restrict__ cur_tokens,
-                                                          const int64_t* __restrict__ eos_ids, int n_eos,
-                                                          int32_t* __restrict__ finished, int32_t* __restrict__ done_count) {
-    const int b = blockIdx.x;
-    float bv = pv[b * AM_BLOCKS + threadIdx.x];
-    int bi = pi[b * AM_BLOCKS + threadIdx.x];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        am_better(bv, bi, ov, oi);
-    }
-    if (threadIdx.x == 0) {
-        const int step = step_dev ? step_dev[0] : 0;
-        if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = bi;
-        if (cur_tokens) cur_tokens[b] = bi;
-        // greedy stopping criterion on the device (HF: EosTokenCriteria over eos_token_id, a list): the FIRST step at which row b
-        // produced an end-of-sequence id is latched in finished[b] (-1 = still running), and done_count counts the latched rows —
-        // the host's "is every row done" poll reads one int instead of scanning the token matrix (entries < 0 of eos_ids never match)
-        if (finished && eos_ids && finished[b] < 0) {
-            bool hit = false;
-            for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)bi);
-            if (hit) {
-                finished[b] = step;
-                if (done_count) atomicAdd(done_count, 1);
-            }
+// Per-block half of logsumexp, 256 threads: sum exp(x - bv) over the block's elements, bv the block's maximum. each(f) calls
+// f(x) for the calling thread's elements. The four wave sums land in ss (behind a barrier); block_exp_sum4 adds them.
+// An empty block or one of -inf logits only has bv = -inf and sums to 0, never exp(-inf - -inf) = NaN.
+template <typename Each>
+__device__ __forceinline__ void block_exp_sums(float bv, float* ss, Each each) {
+    float s = 0.f;
+    if (bv > -INFINITY) each([&](float x) { s += __expf(x - bv); });
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) ss[threadIdx.x >> 6] = s;
+    __syncthreads();
+}
+
+__device__ __forceinline__ float block_exp_sum4(const float* ss) { return ((ss[0] + ss[1]) + ss[2]) + ss[3]; }
+
+// Per-row half, one wave, lane j holding block j's (max mv, sum *ps): sum_j s_j exp(m_j - M), M the row's maximum
+__device__ __forceinline__ float merge_exp_sums(float mv, float M, const float* ps) {
+    return wave_sum(mv > -INFINITY ? *ps * __expf(mv - M) : 0.f);
+}
+
+// Row b's token of this step: into the token matrix and the current tokens, its log-probabilities into the planes laid out like
+// out_tokens (each may be NULL), and the stopping criterion on the device (HF: EosTokenCriteria over eos_token_id, a list): the
+// FIRST step at which row b produced an end-of-sequence id is latched in finished[b] (-1 = still running), and done_count counts the
+// latched rows — the host's "is every row done" poll reads one int instead of scanning the token matrix (entries < 0 of eos_ids
+// never match).
+__device__ __forceinline__ void commit_token(int b, int tok, int step, int64_t* out_tokens, int64_t out_stride, int64_t* cur_tokens,
+                                             const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count,
+                                             float* lp_raw, float* lp_warped, float raw, float warped) {
+    if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = tok;
+    if (cur_tokens) cur_tokens[b] = tok;
+    if (lp_raw) lp_raw[(int64_t)b * out_stride + step] = raw;
+    if (lp_warped) lp_warped[(int64_t)b * out_stride + step] = warped;
+    if (finished && eos_ids && finished[b] < 0) {
+        bool hit = false;
+        for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)tok);
+        if (hit) {
+            finished[b] = step;
+            if (done_count) atomicAdd(done_count, 1);
         }
     }
 }
 
-// argmax with the chosen token's log-probability (gar_argmax_lp): kernels of their own, so gar_argmax's two stay as they are.
-// Stage 1 is argmax_partial_kernel plus, per block, s = sum exp(x - block max) (a second pass over the block's ~V/64 logits, which
-// the first just pulled into the cache); stage 2 merges the 64 (max, s) pairs: sum_j s_j exp(m_j - M). The chosen token IS the
-// maximum, so log p = -log of that sum. Fixed-shape reductions throughout (xor tree in a wave, waves in order): deterministic.
-// An empty block (V < 64 x per) or one of -inf logits only holds (-inf, 0) and contributes 0, never exp(-inf - -inf) = NaN.
-template <typename T>
-__global__ __launch_bounds__(256) void argmax_lp_partial_kernel(const T* __restrict__ logits, int64_t ld, int V,
-                                                                float* __restrict__ pv, int* __restrict__ pi,
-                                                                float* __restrict__ ps) {
+// ---------------------------------------------------------------------------------------------------------------
+// argmax: stage 1 = AM_BLOCKS partial (max, first index) per row; stage 2 = one wave per row.
+// LP (gar_argmax_lp): the instantiations that also write the chosen token's log-probability. Stage 1 adds, per block,
+// s = sum exp(x - block max) (a second pass over the block's ~V/64 logits, which the first just pulled into the cache) into ps;
+// stage 2 merges the 64 (max, s) pairs. The chosen token IS the maximum, so log p = -log of that sum. LP = false (gar_argmax)
+// reads neither ps nor the planes.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T, bool LP>
+__global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict__ logits, int64_t ld, int V,
+                                                             float* __restrict__ pv, int* __restrict__ pi,
+                                                             float* __restrict__ ps) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ float ss[4];
@@ -284,66 +280,44 @@ __global__ __launch_bounds__(256) void argmax_lp_partial_kernel(const T* __restr
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = lo + threadIdx.x; i < hi; i += 256) am_better(bv, bi, DT<T>::ld(row + i), i);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        am_better(bv, bi, ov, oi);
-    }
+    wave_best(bv, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
-    bv = sv[0];
-    bi = si[0];
-    for (int w = 1; w < 4; ++w) am_better(bv, bi, sv[w], si[w]);      // every thread: the block's (max, first index)
-    float s = 0.f;
-    if (bv > -INFINITY)
-        for (int i = lo + threadIdx.x; i < hi; i += 256) s += __expf(DT<T>::ld(row + i) - bv);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) ss[threadIdx.x >> 6] = s;
-    __syncthreads();
+    if (LP || threadIdx.x == 0) {                   // the block's (max, first index): LP in every thread, for the sum
+        if constexpr (LP) { bv = sv[0]; bi = si[0]; }
+        for (int w = 1; w < 4; ++w) am_better(bv, bi, sv[w], si[w]);
+    }
+    if constexpr (LP)
+        block_exp_sums(bv, ss, [&](auto f) {
+            for (int i = lo + threadIdx.x; i < hi; i += 256) f(DT<T>::ld(row + i));
+        });
     if (threadIdx.x == 0) {
         pv[b * AM_BLOCKS + blk] = bv;
         pi[b * AM_BLOCKS + blk] = bi;
-        ps[b * AM_BLOCKS + blk] = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+        if constexpr (LP) ps[b * AM_BLOCKS + blk] = block_exp_sum4(ss);
     }
 }
 
-__global__ __launch_bounds__(64) void argmax_lp_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
-                                                             const float* __restrict__ ps, int64_t* __restrict__ out_tokens,
-                                                             int64_t out_stride, const int32_t* __restrict__ step_dev,
-                                                             int64_t* __restrict__ cur_tokens,
-                                                             const int64_t* __restrict__ eos_ids, int n_eos,
-                                                             int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
-                                                             float* __restrict__ lp_raw, float* __restrict__ lp_warped) {
+template <bool LP>
+__global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
+                                                          const float* __restrict__ ps, int64_t* __restrict__ out_tokens,
+                                                          int64_t out_stride, const int32_t* __restrict__ step_dev,
+                                                          int64_t* __restrict__ cur_tokens,
+                                                          const int64_t* __restrict__ eos_ids, int n_eos,
+                                                          int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
+                                                          float* __restrict__ lp_raw, float* __restrict__ lp_warped) {
     const int b = blockIdx.x;
     const float mv = pv[b * AM_BLOCKS + threadIdx.x];
     float bv = mv;
     int bi = pi[b * AM_BLOCKS + threadIdx.x];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        am_better(bv, bi, ov, oi);
-    }
-    float s = mv > -INFINITY ? ps[b * AM_BLOCKS + threadIdx.x] * __expf(mv - bv) : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    wave_best(bv, bi);
+    float s = 0.f;
+    if constexpr (LP) s = merge_exp_sums(mv, bv, &ps[b * AM_BLOCKS + threadIdx.x]);
     if (threadIdx.x == 0) {
         const int step = step_dev ? step_dev[0] : 0;
-        if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = bi;
-        if (cur_tokens) cur_tokens[b] = bi;
         const float lp = 0.f - logf(s);             // x[tok] - max = 0: HF's processed scores of greedy search are the raw logits
-        if (lp_raw) lp_raw[(int64_t)b * out_stride + step] = lp;
-        if (lp_warped) lp_warped[(int64_t)b * out_stride + step] = lp;
-        if (finished && eos_ids && finished[b] < 0) {        // the stopping criterion, as in argmax_final_kernel
-            bool hit = false;
-            for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)bi);
-            if (hit) {
-                finished[b] = step;
-                if (done_count) atomicAdd(done_count, 1);
-            }
-        }
+        commit_token(b, bi, step, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
+                     LP ? lp_raw : nullptr, LP ? lp_warped : nullptr, lp, lp);      // LP = false: no plane code is compiled
     }
 }
 
@@ -388,7 +362,8 @@ __device__ __forceinline__ unsigned int philox_first(unsigned int c0, unsigned i
 
 // LP (gar_sample_lp): the instantiation that also writes the drawn token's log-probabilities — raw = x[tok] - logsumexp(x[0:V]) over the
 // logits as stored, warped = z[tok] - max z - log Z2 over the kept set (the distribution the draw was taken from) — into planes laid
-// out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false compiles to what it was.
+// out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false (gar_sample) makes no such pass
+// and writes no plane.
 template <typename T, bool LP>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V,
                                                              int64_t* __restrict__ out_tokens, int64_t out_stride,
@@ -411,8 +386,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
     const float temp = temperature > 0.f ? temperature : 1.0f;             // (the host refuses temperature <= 0, as HF does)
     auto zof = [&](int i) { return DT<T>::ld(row + i) / temp; };
     auto block_sum = [&](float v) -> float {        // fixed shape: xor tree inside a wave, waves in order
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        v = wave_sum(v);
         __syncthreads();
         if (lane == 0) red_f[wave] = v;
         __syncthreads();
@@ -423,8 +397,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
     // ---- max
     float mx = -INFINITY;
     for (int i = tid; i < V; i += SMP_THREADS) mx = fmaxf(mx, zof(i));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = wave_max(mx);
     if (lane == 0) red_f[wave] = mx;
     __syncthreads();
     mx = red_f[0];
@@ -600,58 +573,72 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
             for (int i = V - 1; i >= 0; --i)
                 if (smp_key(zof(i)) >= key_lo) { tok = i; break; }
         }
-        if (tok >= 0) {
-            if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = tok;
-            if (cur_tokens) cur_tokens[b] = tok;
-            if constexpr (LP) {                            // every exit above ends here with its tok: one place writes the planes
-                if (lp_raw) lp_raw[(int64_t)b * out_stride + step] = (DT<T>::ld(row + tok) - xs) - logf(Zraw);
-                if (lp_warped) lp_warped[(int64_t)b * out_stride + step] = (zof(tok) - mx) - logf(sh_f[2]);
+        if (tok >= 0) {                                    // every exit above ends here with its tok: one place commits it
+            float raw = 0.f, warped = 0.f;
+            if constexpr (LP) {
+                raw = (DT<T>::ld(row + tok) - xs) - logf(Zraw);
+                warped = (zof(tok) - mx) - logf(sh_f[2]);
             }
-            if (finished && eos_ids && finished[b] < 0) {
-                bool hit = false;
-                for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)tok);
-                if (hit) {
-                    finished[b] = step;
-                    if (done_count) atomicAdd(done_count, 1);
-                }
-            }
+            commit_token(b, tok, step, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
+                         LP ? lp_raw : nullptr, LP ? lp_warped : nullptr, raw, warped);
         }
     }
+}
+
+template <bool LP>
+static int sample_launch(const char* who, int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
+                         int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev,
+                         const int64_t* seed_dev, const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count,
+                         int row_offset, float* lp_raw, float* lp_warped, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0, "%s: bad args", who);
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "%s: eos_ids / finished", who);
+    if (LP) GAR_CHECK_ARG(lp_raw || lp_warped, "%s: no log-probability plane (gar_sample is the form without)", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((sample_kernel<bf16_t, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
+                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+    else
+        hipLaunchKernelGGL((sample_kernel<float, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
+                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
 }
 
 extern "C" int gar_sample(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
                           const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
                           const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
                           gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0, "sample: bad args");
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample: eos_ids / finished");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t, false>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, (float*)nullptr,
-                           (float*)nullptr);
-    else
-        hipLaunchKernelGGL((sample_kernel<float, false>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, (float*)nullptr,
-                           (float*)nullptr);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+    return sample_launch<false>("sample", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev,
+                                eos_ids, n_eos, finished, done_count, row_offset, nullptr, nullptr, stream);
 }
 
 extern "C" int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
                              const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
                              float* lp_raw, float* lp_warped, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0, "sample_lp: bad args");
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample_lp: eos_ids / finished");
-    GAR_CHECK_ARG(lp_raw || lp_warped, "sample_lp: no log-probability plane (gar_sample is the form without)");
+    return sample_launch<true>("sample_lp", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev,
+                               eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped, stream);
+}
+
+// workspace: pv | pi (gar_argmax), pv | pi | ps (gar_argmax_lp), AM_BLOCKS entries per row each
+template <bool LP>
+static int argmax_launch(const char* who, int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
+                         int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace, const int64_t* eos_ids,
+                         int n_eos, int32_t* finished, int32_t* done_count, float* lp_raw, float* lp_warped, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0 && (out_tokens || cur_tokens), "%s: bad args", who);
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "%s: eos_ids / finished", who);
+    if (LP) GAR_CHECK_ARG(lp_raw || lp_warped, "%s: no log-probability plane (gar_argmax is the form without)", who);
+    float* pv = (float*)workspace;
+    int* pi = (int*)(pv + (int64_t)B * AM_BLOCKS);
+    float* ps = LP ? pv + (int64_t)B * AM_BLOCKS * 2 : nullptr;
     hipStream_t s = (hipStream_t)stream;
+    dim3 grid(AM_BLOCKS, B);
     if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t, true>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+        hipLaunchKernelGGL((argmax_partial_kernel<bf16_t, LP>), grid, dim3(256), 0, s, (const bf16_t*)logits, ld, V, pv, pi, ps);
     else
-        hipLaunchKernelGGL((sample_kernel<float, true>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+        hipLaunchKernelGGL((argmax_partial_kernel<float, LP>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi, ps);
+    hipLaunchKernelGGL(argmax_final_kernel<LP>, dim3(B), dim3(64), 0, s, pv, pi, ps, out_tokens, out_stride, step_dev, cur_tokens,
+                       eos_ids, n_eos, finished, done_count, lp_raw, lp_warped);
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }
@@ -664,20 +651,8 @@ extern "C" int64_t gar_argmax_workspace(int B, int V) {
 extern "C" int gar_argmax(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
                           int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace,
                           const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0 && (out_tokens || cur_tokens), "argmax: bad args");
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "argmax: eos_ids / finished");
-    float* pv = (float*)workspace;
-    int* pi = (int*)(pv + (int64_t)B * AM_BLOCKS);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(AM_BLOCKS, B);
-    if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((argmax_partial_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)logits, ld, V, pv, pi);
-    else
-        hipLaunchKernelGGL((argmax_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi);
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(B), dim3(64), 0, s, pv, pi, out_tokens, out_stride, step_dev, cur_tokens, eos_ids,
-                       n_eos, finished, done_count);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+    return argmax_launch<false>("argmax", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids,
+                                n_eos, finished, done_count, nullptr, nullptr, stream);
 }
 
 extern "C" int64_t gar_argmax_lp_workspace(int B, int V) {
@@ -689,22 +664,8 @@ extern "C" int gar_argmax_lp(int dtype, const void* logits, int64_t ld, int B, i
                              int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace,
                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, float* lp_raw,
                              float* lp_warped, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0 && (out_tokens || cur_tokens), "argmax_lp: bad args");
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "argmax_lp: eos_ids / finished");
-    GAR_CHECK_ARG(lp_raw || lp_warped, "argmax_lp: no log-probability plane (gar_argmax is the form without)");
-    float* pv = (float*)workspace;
-    int* pi = (int*)(pv + (int64_t)B * AM_BLOCKS);
-    float* ps = pv + (int64_t)B * AM_BLOCKS * 2;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(AM_BLOCKS, B);
-    if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((argmax_lp_partial_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)logits, ld, V, pv, pi, ps);
-    else
-        hipLaunchKernelGGL((argmax_lp_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi, ps);
-    hipLaunchKernelGGL(argmax_lp_final_kernel, dim3(B), dim3(64), 0, s, pv, pi, ps, out_tokens, out_stride, step_dev, cur_tokens,
-                       eos_ids, n_eos, finished, done_count, lp_raw, lp_warped);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+    return argmax_launch<true>("argmax_lp", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids,
+                               n_eos, finished, done_count, lp_raw, lp_warped, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -714,9 +675,10 @@ extern "C" int gar_argmax_lp(int dtype, const void* logits, int64_t ld, int B, i
 // strictly AFTER round r-1's winner in that order (tk_after), so the elements stay untouched in registers (static indexing, no
 // scratch), ties and -inf logits keep their index order, and an exhausted block answers (-inf, TK_NONE) from then on.
 // Stage 1, grid (AM_BLOCKS, B): a block's ~V/64 logits in TK_ITEMS registers per thread (ITEMS = 0: V > 64 x 256 x TK_ITEMS, re-read
-// from the cache every round), its k best, and sum exp(x - block max) as argmax_lp_partial_kernel forms it. Stage 2, one block per
-// row: the 64 (max, sum) pairs merged as argmax_lp_final_kernel merges them, the 64 x k candidates selected the same way, the
-// candidate ids gathered from the row. Fixed-shape reductions (xor tree in a wave, waves in order), no atomics: deterministic.
+// from the cache every round), its k best, and sum exp(x - block max) by argmax_partial_kernel<T, true>'s block_exp_sums. Stage 2, one
+// block per row: the 64 (max, sum) pairs merged by argmax_final_kernel<true>'s merge_exp_sums — entry 0's value is gar_argmax_lp's
+// lp_raw bit for bit — the 64 x k candidates selected the same way, the candidate ids gathered from the row. Fixed-shape reductions
+// (xor tree in a wave, waves in order), no atomics: deterministic.
 // ---------------------------------------------------------------------------------------------------------------
 #define TK_MAX 32
 #define TK_CAND_MAX 64
@@ -735,18 +697,9 @@ __device__ __forceinline__ void tk_select(int k, float (*sv)[4], int (*si)[4], L
     const int wave = threadIdx.x >> 6;
     float lv, wv;
     int li, wi;
-    auto wave_best = [&]() {
-        wv = lv;
-        wi = li;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(wv, o, 64);
-            const int oi = __shfl_xor(wi, o, 64);
-            am_better(wv, wi, ov, oi);
-        }
-    };
+    auto wave_of_local = [&]() { wv = lv; wi = li; wave_best(wv, wi); };
     local(INFINITY, -1, lv, li);
-    wave_best();
+    wave_of_local();
     for (int r = 0; r < k; ++r) {
         if ((threadIdx.x & 63) == 0) { sv[r & 1][wave] = wv; si[r & 1][wave] = wi; }
         __syncthreads();
@@ -764,7 +717,7 @@ __device__ __forceinline__ void tk_select(int k, float (*sv)[4], int (*si)[4], L
         }
         if (bw == wave) {
             if (li == bi) local(bv, bi, lv, li);
-            wave_best();
+            wave_of_local();
         }
     }
 }
@@ -815,23 +768,17 @@ __global__ __launch_bounds__(256) void topk_lp_partial_kernel(const T* __restric
             if (r == 0) m0 = v;
             if (tid == 0) { rv[r] = v; ri[r] = i; }
         });
-    // sum exp(x - block max): argmax_lp_partial_kernel's sum, term for term (an empty or all -inf block: 0, never exp(-inf - -inf))
-    float s = 0.f;
-    if (m0 > -INFINITY) {
+    block_exp_sums(m0, ss, [&](auto f) {
         if constexpr (ITEMS > 0) {
 #pragma unroll
             for (int j = 0; j < ITEMS; ++j)
-                if (lo + tid + 256 * j < hi) s += __expf(x[j] - m0);
+                if (lo + tid + 256 * j < hi) f(x[j]);
         } else {
-            for (int i = lo + tid; i < hi; i += 256) s += __expf(DT<T>::ld(row + i) - m0);
+            for (int i = lo + tid; i < hi; i += 256) f(DT<T>::ld(row + i));
         }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 63) == 0) ss[tid >> 6] = s;
-    __syncthreads();
+    });
     if (tid < k) { ov[tid] = rv[tid]; oi[tid] = ri[tid]; }
-    if (tid == 0) ps[b * AM_BLOCKS + blk] = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+    if (tid == 0) ps[b * AM_BLOCKS + blk] = block_exp_sum4(ss);
 }
 
 // kw = the k of stage 1 (>= 1: the row maximum is its entry 0 also when only candidates are asked for), k = entries to write (0: none)
@@ -852,14 +799,10 @@ __global__ __launch_bounds__(256) void topk_lp_final_kernel(const T* __restrict_
     const int step = step_dev ? step_dev[0] : 0;
     cv += (int64_t)b * AM_BLOCKS * kw;
     ci += (int64_t)b * AM_BLOCKS * kw;
-    if (tid < 64) {                             // the row's (max, sum exp(x - max)) out of the 64 blocks': argmax_lp_final_kernel's merge
+    if (tid < 64) {                             // the row's (max, sum exp(x - max)) out of the 64 blocks'
         const float mv = cv[tid * kw];
-        float M = mv;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
-        float s = mv > -INFINITY ? ps[b * AM_BLOCKS + tid] * __expf(mv - M) : 0.f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const float M = wave_max(mv);
+        const float s = merge_exp_sums(mv, M, &ps[b * AM_BLOCKS + tid]);
         if (tid == 0) { sms[0] = M; sms[1] = logf(s); }
     }
     __syncthreads();

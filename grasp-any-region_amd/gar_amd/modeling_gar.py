@@ -12,10 +12,11 @@ bookkeeping runs on the device, so ``generate`` has no host sync before the firs
 """
 from __future__ import annotations
 
+import gc
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -62,6 +63,28 @@ class GenerateOutput:
     #                                                         by ascending id — entry 0 is the greedy token
     top_logprobs: Optional[torch.Tensor] = None             # f32 [B * N, n, k]: their log-probabilities
     candidate_logprobs: Optional[torch.Tensor] = None       # f32 [B * N, n, C]: log-probabilities of candidate_token_ids, in their order
+
+
+class _PickTargets(NamedTuple):
+    """where a pick (GARModel._pick) writes: the token matrix, the current tokens and the eos latches of its rows, the batch row of
+    its first row (the Philox row counter of a draw), the (raw, warped) log-probability planes of a return_logprobs request or
+    None, and the planes of a top_logprobs / candidate_token_ids request (GARModel._topk_planes) or None."""
+    out_tokens: torch.Tensor
+    cur: torch.Tensor
+    finished: torch.Tensor
+    row0: int
+    lp: Optional[tuple]
+    tk: Optional[dict]
+
+    @classmethod
+    def of(cls, st, out_tokens) -> "_PickTargets":          # every row of a state
+        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"))
+
+    def rows(self, r0: int, r1: int) -> "_PickTargets":
+        """cut to rows r0 .. r1 - 1: a prompt chunk's first-token head"""
+        tk = self.tk and dict(self.tk, **{n: self.tk[n][r0:r1] for n in ("ids", "lp", "cand_lp") if self.tk[n] is not None})
+        return _PickTargets(self.out_tokens[r0:r1], self.cur[r0:r1], self.finished[r0:r1], self.row0 + r0,
+                            self.lp and tuple(p[r0:r1] for p in self.lp), tk)
 
 
 def logprob_outputs(raw: torch.Tensor, warped: torch.Tensor, finished_at: Sequence[Optional[int]]):
@@ -1308,24 +1331,19 @@ class GARModel:
                 memo[key] = t
         return t
 
-    def _head(self, last_rows: torch.Tensor, B: int, out_tokens, st, cur=None, normed: Optional[torch.Tensor] = None,
-              finished=None, row0: int = 0, decode: bool = False, pick: bool = True, lp=None, tk=None):
-        """final RMSNorm + lm_head + greedy argmax of the given [B, C] rows (row-strided view allowed). ``normed``: the
-        rows after the final norm, when the caller's last launch produced them already (split-K decode path). ``decode``: a
-        decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token. ``pick`` False:
-        the logits only — the caller draws the tokens (N draws per prompt row: _generate_begin_fanout). ``lp``: the (raw, warped)
-        log-probability planes of a return_logprobs request, sliced like ``out_tokens`` — the picking launch is then the one that
-        also writes the chosen token's log-probability (gar_argmax_lp / gar_sample_lp). ``tk``: the planes of a top_logprobs /
-        candidate_token_ids request for these rows (:meth:`_topk_planes`) — one gar_topk_lp beside the pick; it reads the logits only."""
+    def _head(self, last_rows: torch.Tensor, B: int, st, to: Optional["_PickTargets"], normed: Optional[torch.Tensor] = None,
+              decode: bool = False):
+        """final RMSNorm + lm_head of the given [B, C] rows (row-strided view allowed), then :meth:`_pick` into ``to``; returns the
+        logits. ``to`` None: the logits only — the caller draws the tokens (N draws per prompt row: _generate_begin_fanout).
+        ``normed``: the rows after the final norm, when the caller's last launch produced them already (split-K decode path).
+        ``decode``: a decode step's head (the e4m3 lm_head of a decode_weight_dtype="fp8" model), not the prompt's first token."""
         gemm = self._gemm_w8 if decode and self.w_fp8 else ops.gemm
-        cur = st["cur"] if cur is None else cur
         t = self.config.mllm_config.text_config
         C_l, V = t.hidden_size, t.vocab_size
         key = ("head", B, st.get("slot", 0))       # per slot: a pipelined prefill's first-token head runs beside the other slot's decode
         xn = self._buf(key, "xn", (B, C_l))
         Vld = _round_up(V, 64)
         logits = self._buf(key, "logits", (B, Vld))
-        ws = self._buf(key, "amws", (ops.argmax_workspace(B, V),), torch.uint8)
         if normed is not None:
             gemm(normed, self.lm_head, logits)
         elif B <= 16:       # RMSNorm folded into the GEMV prologue; for more rows one tiny norm launch is cheaper
@@ -1333,22 +1351,28 @@ class GARModel:
         else:
             ops.rmsnorm(last_rows, self.final_norm, t.rms_norm_eps, out=xn)
             gemm(xn, self.lm_head, logits)
-        if tk is not None:
-            self._topk_launch(logits, V, st, tk, key)
-        if not pick:
-            return logits
-        fin = st["finished"] if finished is None else finished
-        raw, warped = (None, None) if lp is None else lp
-        if st.get("sampling"):
-            ops.sample(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, st["sample_params"], st["sample_seed"],
-                       eos_ids=st["eos_ids"], finished=fin, done_count=st["done_count"], row_offset=row0, logprobs=raw,
-                       logprobs_warped=warped)
-        else:
-            if lp is not None:      # one more f32 per partial block: a workspace of its own size
-                ws = self._buf(key, "amws_lp", (ops.argmax_lp_workspace(B, V),), torch.uint8)
-            ops.argmax(logits, V, out_tokens, out_tokens.stride(0), st["counters"][2:3], cur, ws, eos_ids=st["eos_ids"],
-                       finished=fin, done_count=st["done_count"], logprobs=raw, logprobs_warped=warped)
+        if to is not None:
+            self._pick(logits, V, st, to)
         return logits
+
+    def _pick(self, logits, V, st, to: "_PickTargets"):
+        """the token of every row of ``logits`` into ``to``, by the request words of ``st``: one gar_topk_lp first when the request
+        has top_logprobs / candidate_token_ids planes (it reads the logits only), then the draw (gar_sample) or the greedy pick
+        (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp)."""
+        B, tk, step = logits.shape[0], to.tk, st["counters"][2:3]
+        key = ("head", B, st.get("slot", 0))
+        if tk is not None:
+            ws = self._buf(key, f"tkws{tk['k']}", (ops.topk_lp_workspace(B, V, tk["k"]),), torch.uint8)   # by k: a captured step keeps its own
+            ops.topk_lp(logits, V, step, ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"], cand_lp=tk["cand_lp"])
+        raw, warped = to.lp or (None, None)
+        latches = dict(eos_ids=st["eos_ids"], finished=to.finished, done_count=st["done_count"], logprobs=raw, logprobs_warped=warped)
+        if st.get("sampling"):
+            ops.sample(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_params"], st["sample_seed"],
+                       row_offset=to.row0, **latches)
+        else:                       # with planes one more f32 per partial block: a workspace of its own size
+            name, size = ("amws", ops.argmax_workspace) if to.lp is None else ("amws_lp", ops.argmax_lp_workspace)
+            ws = self._buf(key, name, (size(B, V),), torch.uint8)
+            ops.argmax(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, ws, **latches)
 
     def _topk_planes(self, skey, st, shape, k: int, cands):
         """st["tk"] of a request: None without top_logprobs / candidate_token_ids, else the planes gar_topk_lp writes — buffers of the
@@ -1369,19 +1393,6 @@ class GARModel:
             tk["cand_lp"] = self._buf(skey, f"cand_lp{C_}", (R, T, C_), torch.float32, zero=True)
         st["tk"] = tk
         return tk
-
-    @staticmethod
-    def _topk_rows(tk, r0: int, r1: int):
-        """``tk`` with its planes cut to rows r0 .. r1 - 1 (a prompt chunk's first-token head), as ``out_tokens[b0:b1]`` is"""
-        if tk is None:
-            return None
-        return dict(tk, **{n: tk[n][r0:r1] for n in ("ids", "lp", "cand_lp") if tk[n] is not None})
-
-    def _topk_launch(self, logits, V, st, tk, key):
-        B = logits.shape[0]
-        ws = self._buf(key, f"tkws{tk['k']}", (ops.topk_lp_workspace(B, V, tk["k"]),), torch.uint8)   # by k: a captured step keeps its own
-        ops.topk_lp(logits, V, st["counters"][2:3], ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"],
-                    cand_lp=tk["cand_lp"])
 
     def _decode_step(self, st, B: int, Smax: int, out_tokens):
         t = self.config.mllm_config.text_config
@@ -1479,7 +1490,7 @@ class GARModel:
                     xn_ready = True
             else:
                 gemm(ff, ly["down"], h, hip.EPI_RES, residual=h)
-        logits = self._head(h, B, out_tokens, st, normed=normed, decode=True, lp=st.get("lp"), tk=st.get("tk"))
+        logits = self._head(h, B, st, _PickTargets.of(st, out_tokens), normed=normed, decode=True)
         ops.counter_add(st["counters"][0:3], 1)
         return logits
 
@@ -1651,39 +1662,26 @@ class GARModel:
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
                                                return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
                                                state_slot, return_logprobs, top_k_lp, cands)
-        # attention_mask is forwarded to the Llama generate by the reference (modeling_gar.py:418-426). A LEFT-padded batch
-        # (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a
-        # sequence keeps its rows in the padded layout, its RoPE positions count from its first real token and the padding
-        # keys stay hidden (HF: position_ids = cumsum(mask) - 1, causal mask AND attention_mask).
-        left_pad, am_dev = self._left_pad(attention_mask, B, S, validate)
+        left_pad, forced_tokens = self._begin_inputs(input_ids, attention_mask, validate, forced_tokens)
         # KV capacity in buckets of 256 positions: evaluation loops with a different prompt length per item reuse one
         # cache, one token buffer ([B, Smax], sliced) and one captured decode graph per bucket
-        if forced_tokens is not None:
-            forced_tokens = forced_tokens.to(self.device, torch.int64)
         Smax = _round_up(S + max_new_tokens, 256)
         skey, st = self._llm_state(B, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (B, Smax), torch.int64, zero=True)[:, :max_new_tokens]
-        lp = st["lp"] = self._logprob_planes(skey, out_tokens, (B, Smax)) if return_logprobs else None
-        tk = self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
+        st["lp"] = self._logprob_planes(skey, out_tokens, (B, Smax)) if return_logprobs else None
+        self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
         eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
+        to = _PickTargets.of(st, out_tokens)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
-        self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
-        if am_dev is not None:      # validate=False: the mask's left-padded form is checked on the device, flag read by the caller
-            ops.input_check(input_ids.to(self.device, torch.int64).contiguous(), V, None, 0, None, 0, None, self._input_flags,
-                            attn_mask=am_dev)
         for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
                                                   feature_replay_video, video_frame_tokens):
             last = self._prefill(embeds, st, Smax, b0)
-            lg = self._head(last, b1 - b0, out_tokens[b0:b1], st, cur=st["cur"][b0:b1], finished=st["finished"][b0:b1], row0=b0,
-                            lp=None if lp is None else (lp[0][b0:b1], lp[1][b0:b1]), tk=self._topk_rows(tk, b0, b1))
+            lg = self._head(last, b1 - b0, st, to.rows(b0, b1))
             if forced_tokens is not None:
                 st["cur"][b0:b1].copy_(forced_tokens[b0:b1, 0])
             if return_logits:
                 first_logits.append(lg[:, :V].float().clone())
-        all_logits = []
-        if return_logits:
-            all_logits.append(torch.cat(first_logits, 0))
         # counters after prefill: pos = S (position of the next token), kv_len = S+1 (incl. it), step = 1
         # (fills take their value as a kernel argument: no host-to-device copy, nothing the host waits for)
         c = st["counters"]
@@ -1691,11 +1689,35 @@ class GARModel:
         c[1:2].fill_(S + 1)
         c[2:3].fill_(1)
         c[3:4].zero_()
-        eos, eos_first = set(eos_list), (eos_list[0] if eos_list else None)
-        return _PendingGeneration(eos_on_device=eos_on_device, st=st, skey=skey, B=B, Smax=Smax, V=V, out_tokens=out_tokens, max_new_tokens=max_new_tokens,
-                                  eos=eos, eos_first=eos_first, pad_token_id=pad_token_id, return_logits=return_logits,
-                                  all_logits=all_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
-                                  sync_every=sync_every, input_flags=self._input_flags, N=1)
+        return self._begin_pending(first_logits, eos_list, eos_on_device=eos_on_device, st=st, skey=skey, B=B, Smax=Smax,
+                                   out_tokens=out_tokens, max_new_tokens=max_new_tokens, pad_token_id=pad_token_id,
+                                   return_logits=return_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
+                                   sync_every=sync_every, N=1)
+
+    def _begin_inputs(self, input_ids, attention_mask, validate: bool, forced_tokens):
+        """What both begin methods do with a request's inputs before they touch a state: the mask's left padding, forced_tokens
+        moved to the device, and the flag word of the device-side input check with the mask's check launched into it (it reads the
+        ids and the mask and writes the flag only, so its place before the state's zeroing fills is free). Returns (left_pad,
+        forced_tokens). attention_mask is forwarded to the Llama generate by the reference (modeling_gar.py:418-426). A LEFT-padded batch
+        (HF's convention for generation: prompts of different lengths right-aligned, zeros in front) is supported: a sequence keeps
+        its rows in the padded layout, its RoPE positions count from its first real token and the padding keys stay hidden (HF:
+        position_ids = cumsum(mask) - 1, causal mask AND attention_mask)."""
+        B, S = input_ids.shape
+        left_pad, am_dev = self._left_pad(attention_mask, B, S, validate)
+        if forced_tokens is not None:
+            forced_tokens = forced_tokens.to(self.device, torch.int64)
+        self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if am_dev is not None:      # validate=False: the mask's left-padded form is checked on the device, flag read by the caller
+            ops.input_check(input_ids.to(self.device, torch.int64).contiguous(), self.config.mllm_config.text_config.vocab_size,
+                            None, 0, None, 0, None, self._input_flags, attn_mask=am_dev)
+        return left_pad, forced_tokens
+
+    def _begin_pending(self, first_logits, eos_list, **kw) -> "_PendingGeneration":
+        """what both begin methods return: the request's words (``kw``) for :meth:`generate_finish`; ``first_logits`` holds the first
+        tokens' logits per prompt chunk when they were asked for, and is empty otherwise"""
+        return _PendingGeneration(V=self.config.mllm_config.text_config.vocab_size,
+                                  all_logits=[torch.cat(first_logits, 0)] if first_logits else [], eos=set(eos_list),
+                                  eos_first=eos_list[0] if eos_list else None, input_flags=self._input_flags, **kw)
 
     def _logprob_planes(self, skey, out_tokens, shape):
         """(raw, warped) f32 planes of a return_logprobs request: buffers of the state shaped like its token buffer and sliced
@@ -1746,11 +1768,9 @@ class GARModel:
         t = self.config.mllm_config.text_config
         B, S = input_ids.shape
         R, V = B * N, t.vocab_size
-        left_pad, am_dev = self._left_pad(attention_mask, B, S, validate)
-        if forced_tokens is not None:
-            forced_tokens = forced_tokens.to(self.device, torch.int64)
-            if forced_tokens.shape[0] != R:
-                raise ValueError(f"forced_tokens must have B * num_return_sequences = {R} rows, got {forced_tokens.shape[0]}")
+        if forced_tokens is not None and forced_tokens.shape[0] != R:
+            raise ValueError(f"forced_tokens must have B * num_return_sequences = {R} rows, got {forced_tokens.shape[0]}")
+        left_pad, forced_tokens = self._begin_inputs(input_ids, attention_mask, validate, forced_tokens)
         shared = self.dtype in HALF_DTYPES
         if shared:
             Sp, T = _round_up(S, 256), _round_up(max_new_tokens, 64)
@@ -1763,31 +1783,22 @@ class GARModel:
             _, pst = self._llm_state(B, Smax, state_slot)
             skey, st = self._llm_state(R, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (R, Smax - Sp if shared else Smax), torch.int64, zero=True)[:, :max_new_tokens]
-        lp = st["lp"] = self._logprob_planes(skey, out_tokens, (R, Smax - Sp if shared else Smax)) if return_logprobs else None
-        tk = self._topk_planes(skey, st, (R, Smax - Sp if shared else Smax), top_k_lp, list(cands))
+        st["lp"] = self._logprob_planes(skey, out_tokens, (R, Smax - Sp if shared else Smax)) if return_logprobs else None
+        self._topk_planes(skey, st, (R, Smax - Sp if shared else Smax), top_k_lp, list(cands))
         self._arm_state(pst, left_pad, None, None, None)
         eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed)
+        to = _PickTargets.of(st, out_tokens)
         first_logits = []
-        self._input_flags = torch.zeros(1, dtype=torch.int32, device=self.device)
-        if am_dev is not None:
-            ops.input_check(input_ids.to(self.device, torch.int64).contiguous(), V, None, 0, None, 0, None, self._input_flags,
-                            attn_mask=am_dev)
         for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
                                                   feature_replay_video, video_frame_tokens):
             last = self._prefill(embeds, pst, Sp, b0)
-            lg = self._head(last, b1 - b0, None, pst, pick=False).repeat_interleave(N, 0)      # the SAME logits for the N draws
+            lg = self._head(last, b1 - b0, pst, None).repeat_interleave(N, 0)      # the SAME logits for the N draws
             r0, r1 = _fanout_rows(b0, b1, N)
-            if tk is not None:          # the N rows of a prompt carry that prompt's values at step 0
-                self._topk_launch(lg, V, st, self._topk_rows(tk, r0, r1), ("head", r1 - r0, st.get("slot", 0)))
-            ops.sample(lg, V, out_tokens[r0:r1], out_tokens.stride(0), st["counters"][2:3], st["cur"][r0:r1], st["sample_params"],
-                       st["sample_seed"], eos_ids=st["eos_ids"], finished=st["finished"][r0:r1], done_count=st["done_count"],
-                       row_offset=r0, logprobs=None if lp is None else lp[0][r0:r1],
-                       logprobs_warped=None if lp is None else lp[1][r0:r1])
+            self._pick(lg, V, st, to.rows(r0, r1))      # the N rows of a prompt carry that prompt's top-k / candidate values at step 0
             if forced_tokens is not None:
                 st["cur"][r0:r1].copy_(forced_tokens[r0:r1, 0])
             if return_logits:
                 first_logits.append(lg[:, :V].float())
-        all_logits = [torch.cat(first_logits, 0)] if return_logits else []
         c = st["counters"]
         if shared:                      # [t, -, step, P]: the first decode step appends at suffix row 0
             c[2:3].fill_(1)
@@ -1800,11 +1811,10 @@ class GARModel:
             c[0:1].fill_(S)
             c[1:2].fill_(S + 1)
             c[2:3].fill_(1)
-        eos, eos_first = set(eos_list), (eos_list[0] if eos_list else None)
-        return _PendingGeneration(eos_on_device=eos_on_device, st=st, skey=skey, B=R, Smax=Smax, V=V, out_tokens=out_tokens,
-                                  max_new_tokens=max_new_tokens, eos=eos, eos_first=eos_first, pad_token_id=pad_token_id,
-                                  return_logits=return_logits, all_logits=all_logits, forced_tokens=forced_tokens,
-                                  use_graph=use_graph, validate=validate, sync_every=sync_every, input_flags=self._input_flags, N=N)
+        return self._begin_pending(first_logits, eos_list, eos_on_device=eos_on_device, st=st, skey=skey, B=R, Smax=Smax,
+                                   out_tokens=out_tokens, max_new_tokens=max_new_tokens, pad_token_id=pad_token_id,
+                                   return_logits=return_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
+                                   sync_every=sync_every, N=N)
 
     # ---- teacher-forced scoring ---------------------------------------------------------------------------------------
     XENT_CHUNK_ROWS = 8192          # scored rows per fused-head launch: partials workspace <= chunk x 16 KiB at V = 128256
@@ -2030,6 +2040,10 @@ class GARModel:
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize(self.device)
             restore()
+            # a dropped model is a reference cycle (model <-> mllm facade): its captured graphs and their memory pools go when the
+            # cycle collector runs. Inside a capture that is an illegal call and the HIP runtime aborts — and torch.cuda.graph no
+            # longer collects before it captures — so the dead cycles go here, and the step itself creates none that hold a graph
+            gc.collect()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
                 logits = self._decode_step(st, B, Smax, out_tokens)

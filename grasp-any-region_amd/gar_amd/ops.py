@@ -630,6 +630,14 @@ def _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
     return logprobs is not None or logprobs_warped is not None
 
 
+def _latches(B, eos_ids, finished, done_count):
+    """the stopping criterion's four arguments of :func:`argmax` / :func:`sample`: eos table, its length, the two latches"""
+    assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
+    assert finished is None or (eos_ids is not None and finished.dtype == torch.int32 and finished.is_contiguous()
+                                and finished.numel() == B)
+    return ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count)
+
+
 def argmax(logits, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids=None, finished=None, done_count=None,
            logprobs=None, logprobs_warped=None):
     """``eos_ids`` int64 [n] (device, entries < 0 never match), ``finished`` int32 [B] (-1 = running; the kernel latches the step
@@ -638,19 +646,13 @@ def argmax(logits, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, e
     ``out_tokens``; with either one the launch is ``gar_argmax_lp`` (``workspace`` >= :func:`argmax_lp_workspace` bytes), which
     also writes the chosen token's log-probability at the step's column — equal in both planes for greedy search."""
     B = logits.shape[0]
-    assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
-    assert finished is None or (eos_ids is not None and finished.dtype == torch.int32 and finished.is_contiguous()
-                                and finished.numel() == B)
+    head = (dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride, ptr(step_dev),
+            ptr(cur_tokens), ptr(workspace), *_latches(B, eos_ids, finished, done_count))
     if _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
         assert workspace.numel() * workspace.element_size() >= argmax_lp_workspace(B, V)
-        check(lib(logits.dtype).gar_argmax_lp(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens),
-                                              out_stride, ptr(step_dev), ptr(cur_tokens), ptr(workspace), ptr(eos_ids),
-                                              0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count),
-                                              ptr(logprobs), ptr(logprobs_warped), stream()), "gar_argmax_lp")
-        return
-    check(lib(logits.dtype).gar_argmax(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
-                           ptr(step_dev), ptr(cur_tokens), ptr(workspace), ptr(eos_ids),
-                           0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count), stream()), "gar_argmax")
+        check(lib(logits.dtype).gar_argmax_lp(*head, ptr(logprobs), ptr(logprobs_warped), stream()), "gar_argmax_lp")
+    else:
+        check(lib(logits.dtype).gar_argmax(*head, stream()), "gar_argmax")
 
 
 def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed, eos_ids=None, finished=None, done_count=None,
@@ -664,20 +666,12 @@ def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed
     B = logits.shape[0]
     assert params.dtype == torch.float32 and params.numel() >= 3 and params.is_contiguous()
     assert seed.dtype == torch.int64 and seed.numel() >= 1
-    assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
-    assert finished is None or (eos_ids is not None and finished.dtype == torch.int32 and finished.is_contiguous()
-                                and finished.numel() == B)
+    head = (dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride, ptr(step_dev),
+            ptr(cur_tokens), ptr(params), ptr(seed), *_latches(B, eos_ids, finished, done_count), int(row_offset))
     if _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
-        check(lib(logits.dtype).gar_sample_lp(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens),
-                                              out_stride, ptr(step_dev), ptr(cur_tokens), ptr(params), ptr(seed), ptr(eos_ids),
-                                              0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count),
-                                              int(row_offset), ptr(logprobs), ptr(logprobs_warped), stream()), "gar_sample_lp")
-        return
-    check(lib(logits.dtype).gar_sample(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
-                                       ptr(step_dev), ptr(cur_tokens), ptr(params), ptr(seed), ptr(eos_ids),
-                                       0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count), int(row_offset),
-                                       stream()),
-          "gar_sample")
+        check(lib(logits.dtype).gar_sample_lp(*head, ptr(logprobs), ptr(logprobs_warped), stream()), "gar_sample_lp")
+    else:
+        check(lib(logits.dtype).gar_sample(*head, stream()), "gar_sample")
 
 
 def argmax_workspace(B, V) -> int:

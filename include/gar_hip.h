@@ -494,10 +494,10 @@ int gar_sample(int dtype, const void* logits, int64_t ld, int B, int V, int64_t*
                const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset, gar_stream_t stream);
 
 /* ---- Log-probability of the token a step chose (GARModel.generate(return_logprobs=True)) ------------------------------------
- * Additive: three new entry points, gar_argmax / gar_sample keep their signatures and their kernels, so GAR_ABI_VERSION stays 16.
- * gar_argmax_lp / gar_sample_lp do what gar_argmax / gar_sample do — the token, cur_tokens and the eos latches are byte-identical
- * on the same inputs — and, in the same launches, write f32 planes laid out like out_tokens (row stride out_stride, column
- * step_dev[0]; either plane may be NULL, not both):
+ * Additive: three entry points beside gar_argmax / gar_sample, whose signatures stand, so GAR_ABI_VERSION stays 16. Each pair is
+ * two instantiations of one kernel body: gar_argmax_lp / gar_sample_lp do what gar_argmax / gar_sample do — the token, cur_tokens
+ * and the eos latches are byte-identical on the same inputs — and, in the same launches, write f32 planes laid out like out_tokens
+ * (row stride out_stride, column step_dev[0]; either plane may be NULL, not both):
  *   lp_raw     x[tok] - logsumexp(x[0:V]) over the logits as stored (the library's dtype read as f32; columns V..ld-1 are never
  *              read): gar_xent_combine's definition, HF's compute_transition_scores(logits, normalize_logits=True);
  *   lp_warped  the log-probability under the distribution the token was drawn from: z[tok] - max z - log Z2 with z = x / T over
@@ -518,7 +518,7 @@ int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64
  * Additive: two new entry points, GAR_ABI_VERSION stays 16. Per row b of logits [B, ld] (the library's dtype read as f32; columns
  * V..ld-1 are never read), with lp[i] = x[i] - logsumexp(x[0:V]) — gar_argmax_lp's / gar_xent_combine's raw definition:
  *   top-k       1 <= k <= min(32, V): the k largest logits in the order (value descending, index ascending) — gar_argmax's tie rule,
- *               so entry 0 is gar_argmax's token (its value is gar_argmax_lp's lp_raw, formed the same way). Entry r goes to
+ *               so entry 0 is gar_argmax's token (its value is gar_argmax_lp's lp_raw bit for bit: one code forms both). Entry r goes to
  *               top_ids / top_lp [b * top_row_stride + step_dev[0] * top_step_stride + r] (int32 / f32 planes [rows, T, k] of their
  *               own layout; step_dev NULL = step 0). top_ids and top_lp go together; without them k = 0.
  *   candidates  1 <= n_cand <= 64: cand_lp[b * cand_row_stride + step * cand_step_stride + c] = lp[cand_ids[c]] for one device int32

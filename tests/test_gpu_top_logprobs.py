@@ -68,16 +68,23 @@ def _only_step_column_written(plane, sentinel):
 @pytest.mark.parametrize("V", [37, 1000, 128256, 150001])
 def test_topk_lp_kernel_against_f64(dtype, V):
     """k in {1, 5, 20, 32} (k <= V), B = 8: ids equal the float64 reference's exactly (value descending, index ascending — bf16 rows
-    hold many genuine ties), values within LP_TOL with -inf equal to -inf, entry 0 is gar_argmax's token on the same buffer, only
-    the step's column of the wide planes is written, either output group alone gives the same bits. V = 37: 63 of 64 partial blocks
-    hold at most one element and k exceeds it; V = 1000: 16 per block, fewer than k = 20; V = 128256: the real vocabulary;
-    V = 150001: past the in-register form's 64 x 256 x 8 elements, the form that re-reads its block every round."""
+    hold many genuine ties), values within LP_TOL with -inf equal to -inf, entry 0 is gar_argmax's token on the same buffer and its
+    value gar_argmax_lp's lp_raw bit for bit, only the step's column of the wide planes is written, either output group alone gives
+    the same bits. V = 37: 63 of 64 partial blocks hold at most one element and k exceeds it; V = 1000: 16 per block, fewer than
+    k = 20; V = 128256: the real vocabulary; V = 150001: past the in-register form's 64 x 256 x 8 elements, the form that re-reads
+    its block every round."""
     from gar_amd import hip, ops
     hip.require_device(0)
     x, cands, ref_ids, ref_lp, ref_cand = _case(V, dtype)
     cur = torch.zeros(8, dtype=torch.int64, device=x.device)
     ops.argmax(x, V, None, 0, None, cur, torch.empty(ops.argmax_workspace(8, V), dtype=torch.uint8, device=x.device))
     am = cur.cpu()
+    # gar_argmax_lp on the same buffer: its lp_raw is entry 0's value bit for bit (include/gar_hip.h: "formed the same way")
+    out, raw = torch.zeros(8, NCOL, dtype=torch.int64, device=x.device), torch.zeros(8, NCOL, device=x.device)
+    ops.argmax(x, V, out, NCOL, torch.tensor([STEP], dtype=torch.int32, device=x.device), None,
+               torch.empty(ops.argmax_lp_workspace(8, V), dtype=torch.uint8, device=x.device), logprobs=raw)
+    assert torch.equal(out[:, STEP].cpu(), am)
+    lp_raw = raw[:, STEP].cpu()
     worst = 0.0
     for k in (1, 5, 20, 32):
         if k > V:            # none of the sizes above: every V here holds 32 entries
@@ -87,6 +94,7 @@ def test_topk_lp_kernel_against_f64(dtype, V):
         assert torch.equal(ids.long(), ref_ids[:, :k]), (k, ids, ref_ids[:, :k])
         worst = max(worst, close_or_both_minus_inf(lp, ref_lp[:, :k], LP_TOL), close_or_both_minus_inf(cand, ref_cand, LP_TOL))
         assert torch.equal(ids[:, 0].long(), am)
+        assert torch.equal(lp[:, 0], lp_raw), (k, lp[:, 0], lp_raw)
         assert ids[6].tolist() == list(range(k))
         assert ids[7, :3].tolist()[:k] == [5, V // 3, V - 2][:k] and torch.isneginf(lp[7, 3:]).all()
         assert torch.isneginf(cand[7, [0, 1, 3]]).all()

@@ -173,6 +173,7 @@ def main():
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
+        f.write("\n")
     print(json.dumps(res))
 
 
