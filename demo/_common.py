@@ -40,6 +40,10 @@ def base_parser(description):
     ap.add_argument("--top_logprobs", type=int, default=0, metavar="K",
                     help="print, under each output and per generated token, the K most likely tokens as decoded-token:probability "
                          "(raw softmax of the step's logits, also when sampling; K <= 32)")
+    ap.add_argument("--repetition_penalty", type=float, default=1.0,
+                    help="HF's repetition penalty over the tokens generated so far (1.0 = off; e.g. 1.2 against a looping caption)")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0, metavar="N",
+                    help="no N-gram of the generated tokens occurs twice (0 = off)")
     ap.add_argument("--synthetic_weights", action="store_true",
                     help="seeded random weights of the named size + the stub tokenizer (plumbing / benchmarking)")
     return ap
@@ -80,6 +84,14 @@ def generation_config(args, processor):
 def sampling_kwargs(args, gc):
     """generate() keywords that go with :func:`generation_config`: the request's Philox key when it samples"""
     return dict(seed=args.seed) if gc.get("do_sample") else {}
+
+
+def logits_processing_kwargs(args):
+    """generate() keywords of --repetition_penalty / --no_repeat_ngram_size: the logits_processing parameter when either acts"""
+    from gar_amd import LogitsProcessing
+    lp = LogitsProcessing(repetition_penalty=getattr(args, "repetition_penalty", 1.0),
+                          no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0))
+    return {} if lp.neutral else dict(logits_processing=lp)
 
 
 def top_logprob_lines(out, row, tokenizer):

@@ -4,7 +4,7 @@
 import numpy as np
 from PIL import Image
 
-from _common import base_parser, generation_config, load, sampling_kwargs, top_logprob_lines
+from _common import base_parser, generation_config, load, logits_processing_kwargs, sampling_kwargs, top_logprob_lines
 
 
 def main():
@@ -26,7 +26,7 @@ def main():
     data_sample = dataset[0]
     gc = generation_config(args, processor)
     out = model.generate(**data_sample, generation_config=gc, return_dict=True, top_logprobs=args.top_logprobs,
-                         **sampling_kwargs(args, gc))
+                         **sampling_kwargs(args, gc), **logits_processing_kwargs(args))
     for r, seq in enumerate(out.sequences):     # one answer, or the --num_return_sequences sampled ones
         print(processor.tokenizer.decode(seq, skip_special_tokens=True).strip())
         if args.top_logprobs:

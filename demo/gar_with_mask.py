@@ -4,7 +4,7 @@ demo/gar_with_mask.py (same flags: --model_name_or_path --image_path --mask_path
 import numpy as np
 from PIL import Image
 
-from _common import base_parser, generation_config, load, sampling_kwargs, top_logprob_lines
+from _common import base_parser, generation_config, load, logits_processing_kwargs, sampling_kwargs, top_logprob_lines
 
 
 def main():
@@ -26,7 +26,7 @@ def main():
     data_sample = dataset[0]
     gc = generation_config(args, processor)
     out = model.generate(**data_sample, generation_config=gc, return_dict=True, return_logprobs=args.return_logprobs,
-                         top_logprobs=args.top_logprobs, **sampling_kwargs(args, gc))
+                         top_logprobs=args.top_logprobs, **sampling_kwargs(args, gc), **logits_processing_kwargs(args))
     if args.return_logprobs:                # the model's own confidence in each caption: mean log-probability of its tokens
         mean = (out.sum_logprobs / out.n_tokens.clamp(min=1)).tolist()
         for r in sorted(range(len(mean)), key=lambda i: -mean[i]):

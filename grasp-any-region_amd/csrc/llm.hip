@@ -888,3 +888,114 @@ extern "C" int gar_topk_lp(int dtype, const void* logits, int64_t ld, int B, int
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Logits processors of a step (gar_logits_process): HF's RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor,
+// NoBadWordsLogitsProcessor, MinNewTokensLengthLogitsProcessor, SuppressTokensLogitsProcessor and
+// SuppressTokensAtBeginLogitsProcessor over a row's own generated tokens (out_tokens[b][0:t], t = step_dev[0]), as sparse edits of
+// the row in place before the pick. One 1024-thread workgroup per row and two bitmaps over the vocabulary in LDS (2 x 4 bytes per
+// 32 ids: 32 KB at V = 128256): phase 1 marks — history ids into `pen` (LDS atomic OR: a token that occurs a hundred times sets one
+// bit), every banned id into `ban`; phase 2, behind one barrier, gives each thread bitmap words of its own, so every marked entry is
+// read once (the value stored before the launch), computed once and written once by exactly one thread: no compounding, no two
+// writers. Unmarked entries and the columns V..ld-1 are never touched. The bans are -inf and a penalised -inf stays -inf, so HF's
+// list order among these processors does not show in the result. Every read of the parameter block is bounded by params_words,
+// every read of the history by out_cols, every marked id by V.
+// ---------------------------------------------------------------------------------------------------------------
+#define LP_THREADS 1024
+#define LP_HEADER 8                 // params: [penalty f32 bits, n, m, n_suppress, n_begin, n_bad, n_bad_tokens, 0] then the lists
+#define LP_MAX_VOCAB 262144         // two bitmaps in 64 KB of LDS
+
+template <typename T>
+__global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(T* __restrict__ logits, int64_t ld, int V,
+                                                                    const int64_t* __restrict__ out_tokens, int64_t out_stride,
+                                                                    int out_cols, const int32_t* __restrict__ step_dev,
+                                                                    const int64_t* __restrict__ eos_ids, int n_eos,
+                                                                    const int32_t* __restrict__ params, int params_words) {
+    extern __shared__ unsigned int lp_bits[];
+    const int W = (V + 31) >> 5;
+    unsigned int* pen = lp_bits;
+    unsigned int* ban = lp_bits + W;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    for (int w = tid; w < 2 * W; w += LP_THREADS) lp_bits[w] = 0u;
+    int t = step_dev ? step_dev[0] : 0;
+    t = out_tokens ? max(0, min(t, out_cols)) : 0;
+    const int64_t* hist = out_tokens + (int64_t)b * out_stride;
+    const float p = __int_as_float(params[0]);
+    const int n = params[1], m = params[2];
+    int n_sup = params[3], n_beg = params[4], n_bad = params[5], n_bt = params[6];
+    // the lists, in this order behind the header; a block that does not fit its buffer names no list
+    const bool lists_ok = n_sup >= 0 && n_beg >= 0 && n_bad >= 0 && n_bt >= 0 &&
+                          (int64_t)LP_HEADER + n_sup + n_beg + (n_bad ? n_bad + 1 : 0) + n_bt <= (int64_t)params_words;
+    if (!lists_ok) n_sup = n_beg = n_bad = n_bt = 0;
+    const int32_t* sup = params + LP_HEADER;
+    const int32_t* beg = sup + n_sup;
+    const int32_t* bad_off = beg + n_beg;           // n_bad + 1 offsets into bad_tok
+    const int32_t* bad_tok = bad_off + (n_bad ? n_bad + 1 : 0);
+    __syncthreads();
+    auto mark = [&](unsigned int* bits, int64_t id) {
+        if (id >= 0 && id < V) atomicOr(&bits[id >> 5], 1u << (id & 31));
+    };
+    if (p != 1.0f)
+        for (int j = tid; j < t; j += LP_THREADS) mark(pen, hist[j]);
+    if (n > 0 && t + 1 >= n)                        // an n-gram of the history whose first n - 1 tokens are the history's last n - 1
+        for (int j = tid; j + n <= t; j += LP_THREADS) {
+            bool same = true;
+            for (int k = 0; k < n - 1 && same; ++k) same = hist[j + k] == hist[t - n + 1 + k];
+            if (same) mark(ban, hist[j + n - 1]);
+        }
+    if (t < m)
+        for (int e = tid; e < n_eos; e += LP_THREADS) mark(ban, eos_ids[e]);
+    for (int i = tid; i < n_sup; i += LP_THREADS) mark(ban, sup[i]);
+    if (t == 0)
+        for (int i = tid; i < n_beg; i += LP_THREADS) mark(ban, beg[i]);
+    for (int e = tid; e < n_bad; e += LP_THREADS) {
+        const int o0 = bad_off[e], o1 = bad_off[e + 1], L = o1 - o0;
+        if (o0 < 0 || L < 1 || o1 > n_bt) continue;
+        if (L == 1) { mark(ban, bad_tok[o0]); continue; }
+        if (L > t) continue;                        // HF's SequenceBiasLogitsProcessor skips an entry longer than the context
+        bool same = true;
+        for (int k = 0; k < L - 1 && same; ++k) same = hist[t - (L - 1) + k] == (int64_t)bad_tok[o0 + k];
+        if (same) mark(ban, bad_tok[o1 - 1]);
+    }
+    __syncthreads();
+    T* row = logits + (int64_t)b * ld;
+    for (int w = tid; w < W; w += LP_THREADS) {
+        const unsigned int bw = ban[w];
+        unsigned int bits = pen[w] | bw;
+        while (bits) {
+            const int bit = __ffs(bits) - 1;
+            bits &= bits - 1;
+            const int i = (w << 5) + bit;           // < V: mark() set no bit at or past V
+            if ((bw >> bit) & 1u) {
+                DT<T>::st(row + i, -INFINITY);
+            } else {
+                const float x = DT<T>::ld(row + i);
+                DT<T>::st(row + i, x < 0.f ? x * p : x / p);        // HF: where(x < 0, x * p, x / p) — a true division
+            }
+        }
+    }
+}
+
+extern "C" int gar_logits_process_max_vocab(void) { return LP_MAX_VOCAB; }
+
+extern "C" int gar_logits_process(int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens, int64_t out_stride,
+                                  int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos,
+                                  const int32_t* params_dev, int params_words, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && params_dev && B > 0 && V > 0 && ld >= V, "logits_process: bad args");
+    GAR_CHECK_ARG(V <= LP_MAX_VOCAB, "logits_process: V %d above %d (two vocabulary bitmaps in 64 KB of LDS)", V, LP_MAX_VOCAB);
+    GAR_CHECK_ARG(params_words >= LP_HEADER, "logits_process: a parameter block of %d words, the header alone has %d", params_words,
+                  LP_HEADER);
+    GAR_CHECK_ARG(!out_tokens || (out_cols >= 0 && out_stride >= out_cols), "logits_process: out_cols %d / out_stride %lld", out_cols,
+                  (long long)out_stride);
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids), "logits_process: eos_ids");
+    const size_t lds = (size_t)((V + 31) >> 5) * 8;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL(logits_process_kernel<bf16_t>, dim3(B), dim3(LP_THREADS), lds, s, (bf16_t*)logits, ld, V, out_tokens,
+                           out_stride, out_cols, step_dev, eos_ids, n_eos, params_dev, params_words);
+    else
+        hipLaunchKernelGGL(logits_process_kernel<float>, dim3(B), dim3(LP_THREADS), lds, s, (float*)logits, ld, V, out_tokens,
+                           out_stride, out_cols, step_dev, eos_ids, n_eos, params_dev, params_words);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}

@@ -56,7 +56,11 @@ class ContinuousBatcher:
     def __init__(self, model, slots: int, max_new_tokens: int = 1024, eos_token_id=None, poll_every: int = 8,
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
                  validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False,
-                 top_logprobs: int = 0, candidate_token_ids=None):
+                 top_logprobs: int = 0, candidate_token_ids=None, logits_processing=None):
+        if logits_processing is not None:
+            # the processors read a row's history from columns 0..t-1 of the token matrix; this loop shifts that matrix per row
+            # (_rebase), so a row's column is not its step: not threaded through here
+            raise hip.GarError("ContinuousBatcher: logits_processing is not implemented (call generate(logits_processing=...))")
         if top_logprobs or candidate_token_ids:
             # generate()'s [rows, T, k] planes are addressed by the step's column like the token matrix this loop shifts (_rebase),
             # and pop_finished returns token lists only: not threaded through here
@@ -108,6 +112,8 @@ class ContinuousBatcher:
         if sample.get("top_logprobs") or sample.get("candidate_token_ids"):
             raise hip.GarError("ContinuousBatcher.submit: top_logprobs / candidate_token_ids are not implemented (call "
                                "generate(top_logprobs=..., candidate_token_ids=...))")
+        if sample.get("logits_processing") is not None:
+            raise hip.GarError("ContinuousBatcher.submit: logits_processing is not implemented (call generate(logits_processing=...))")
         if sample.get("return_logprobs"):
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
         t = self._next_ticket

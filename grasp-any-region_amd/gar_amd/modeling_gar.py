@@ -22,6 +22,7 @@ import torch
 
 from . import hip, ops
 from .configuration_gar import GARConfig
+from .logits_processing import LogitsProcessing, _Refused as _ProcessingRefused
 from .planner import plan_chunks
 from .weights import LM, PJ, VT, check_weights, load_weights, normalize_checkpoint, synthetic_weights
 
@@ -256,14 +257,20 @@ def _fanout_rows(b0: int, b1: int, N: int):
     return b0 * N, b1 * N
 
 
+# the refused options that generate(logits_processing=...) provides under a parameter of its own
+_LOGITS_PROCESSING_FIELDS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "min_length", "suppress_tokens",
+                             "begin_suppress_tokens", "bad_words_ids")
+
+
 def _refuse_non_greedy(get):
     for name, neutral in _NEUTRAL_GENERATION_OPTIONS.items():
         v = get(name)
         if name == "num_return_sequences" and get("do_sample", False):
             continue                                        # sampling: read by _num_return_sequences
         if not any((v is n) or (n is not None and not isinstance(v, bool) and v == n) for n in neutral):
+            hint = " — pass generate(logits_processing=LogitsProcessing(...)) instead" if name in _LOGITS_PROCESSING_FIELDS else ""
             raise hip.GarError(f"generation option {name}={v!r} is not implemented (greedy search only: it would change the tokens "
-                               f"and is refused rather than ignored)")
+                               f"and is refused rather than ignored){hint}")
 
 
 def _sampling_options(get):
@@ -1355,12 +1362,46 @@ class GARModel:
             self._pick(logits, V, st, to)
         return logits
 
-    def _pick(self, logits, V, st, to: "_PickTargets"):
-        """the token of every row of ``logits`` into ``to``, by the request words of ``st``: one gar_topk_lp first when the request
+    def _process(self, logits, V, st, out_tokens):
+        """the request's logits processors on ``logits`` in place (one gar_logits_process launch), the rows' histories read from
+        ``out_tokens`` up to the state's step; nothing — no launch — for a request without a non-neutral ``logits_processing``"""
+        if st.get("proc") is not None:
+            if out_tokens is not None:
+                # out_tokens is a [:, :max_new_tokens] slice of the state's token buffer; the captured step serves every
+                # max_new_tokens of the bucket, so the history's bound is the buffer's row (its stride), not the slice's width
+                cap = out_tokens.stride(0)
+                out_tokens = out_tokens.as_strided((out_tokens.shape[0], cap), (cap, 1), out_tokens.storage_offset())
+            ops.logits_process(logits, V, out_tokens, st["counters"][2:3], st["eos_ids"], st["proc"])
+
+    def _arm_processing(self, skey, st, proc: Optional[LogitsProcessing], eos_list, eos_on_device: bool):
+        """st["proc"] of a request: None without (non-neutral) logits_processing, else the state's int32 parameter block with the
+        request's values uploaded — a buffer of the state, so the captured step that reads it serves any values"""
+        st["proc"] = None
+        if proc is None:
+            return
+        V = self.config.mllm_config.text_config.vocab_size
+        if V > ops.logits_process_max_vocab():
+            raise hip.GarError(f"logits_processing: vocab_size {V} above gar_logits_process's {ops.logits_process_max_vocab()}")
+        if proc.min_new_tokens and eos_list and not eos_on_device:
+            raise hip.GarError(f"logits_processing: min_new_tokens with {len(eos_list)} eos ids: the device-side eos table holds "
+                               f"{self.MAX_EOS_IDS}")
+        try:
+            words = proc.pack(V, eos_list)
+        except _ProcessingRefused as e:
+            raise hip.GarError(str(e)) from None
+        buf = self._buf(skey, "proc", (ops.LOGITS_PROCESS_WORDS,), torch.int32, zero=True)
+        buf[:len(words)].copy_(self._upload(words, torch.int32))
+        st["proc"] = buf
+
+    def _pick(self, logits, V, st, to: "_PickTargets", process: bool = True):
+        """the token of every row of ``logits`` into ``to``, by the request words of ``st``: the request's logits processors first
+        (gar_logits_process, in place; ``process`` False: the caller ran them), then one gar_topk_lp when the request
         has top_logprobs / candidate_token_ids planes (it reads the logits only), then the draw (gar_sample) or the greedy pick
         (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp)."""
         B, tk, step = logits.shape[0], to.tk, st["counters"][2:3]
         key = ("head", B, st.get("slot", 0))
+        if process:
+            self._process(logits, V, st, to.out_tokens)
         if tk is not None:
             ws = self._buf(key, f"tkws{tk['k']}", (ops.topk_lp_workspace(B, V, tk["k"]),), torch.uint8)   # by k: a captured step keeps its own
             ops.topk_lp(logits, V, step, ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"], cand_lp=tk["cand_lp"])
@@ -1613,7 +1654,7 @@ class GARModel:
                        return_logits: bool = False, sync_every: int = 16, feature_replay_video: bool = False,
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
-                       top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None,
+                       top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None, logits_processing=None,
                        **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
@@ -1637,7 +1678,27 @@ class GARModel:
         logits by ascending id) and the log-probabilities of the given ids (``candidate_logprobs`` [B * N, n, C]). The
         values are always RAW log-probabilities x[i] - logsumexp(x) of the step's logits, also with ``do_sample=True`` — the warped
         value of the drawn token stays ``token_logprobs_warped``. Columns behind a row's first eos hold id -1 / value 0.0; with
-        ``forced_tokens`` the fields describe the model's own distribution. Independent of ``return_logprobs``; tokens unchanged."""
+        ``forced_tokens`` the fields describe the model's own distribution. Independent of ``return_logprobs``; tokens unchanged.
+
+        ``logits_processing``: a :class:`LogitsProcessing` (or a dict of its fields) — repetition penalty, no-repeat n-gram size,
+        min_new_tokens, suppress / begin-suppress tokens and bad words, HF's processors applied on the device to every step's
+        logits before the pick, or before temperature / top-k / top-p with ``do_sample=True``. As the reference calls
+        HF's generate with ``inputs_embeds`` only, a row's history is its own generated tokens: the prompt is never penalised or
+        scanned. ``return_logits=True`` then returns the processed scores (HF's ``scores``). None or all-neutral values: the path
+        and the launches of a call without it. Refused with ``GarError``: together with ``forced_tokens`` (the fed history would
+        differ from ``sequences``), and with ``return_logprobs`` / ``top_logprobs`` / ``candidate_token_ids`` (defined over the raw
+        logits). The GenerationConfig fields of the same names stay refused."""
+        proc = LogitsProcessing.coerce(logits_processing)
+        proc = None if proc.neutral else proc
+        if proc is not None:
+            if forced_tokens is not None:
+                raise hip.GarError("logits_processing with forced_tokens is not implemented (the processors read the history from the "
+                                   "token matrix, which would differ from the tokens fed back)")
+            for name, on in (("return_logprobs", return_logprobs), ("top_logprobs", top_logprobs),
+                             ("candidate_token_ids", candidate_token_ids)):
+                if on:
+                    raise hip.GarError(f"logits_processing with {name} is not implemented ({name} is defined over the unprocessed "
+                                       "logits, DESIGN 7.5 / 7.6; over processed scores it is a follow-up)")
         top_k_lp, cands = top_logprob_options(top_logprobs, candidate_token_ids, self.config.mllm_config.text_config.vocab_size)
         sampling = None
         N = 1
@@ -1661,7 +1722,7 @@ class GARModel:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
                                                return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
-                                               state_slot, return_logprobs, top_k_lp, cands)
+                                               state_slot, return_logprobs, top_k_lp, cands, proc)
         left_pad, forced_tokens = self._begin_inputs(input_ids, attention_mask, validate, forced_tokens)
         # KV capacity in buckets of 256 positions: evaluation loops with a different prompt length per item reuse one
         # cache, one token buffer ([B, Smax], sliced) and one captured decode graph per bucket
@@ -1671,6 +1732,7 @@ class GARModel:
         st["lp"] = self._logprob_planes(skey, out_tokens, (B, Smax)) if return_logprobs else None
         self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
         eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
+        self._arm_processing(skey, st, proc, eos_list, eos_on_device)
         to = _PickTargets.of(st, out_tokens)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
@@ -1758,7 +1820,7 @@ class GARModel:
     def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate, return_logits,
                                sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot,
-                               return_logprobs=False, top_k_lp=0, cands=()):
+                               return_logprobs=False, top_k_lp=0, cands=(), proc=None):
         """generate_begin of a num_return_sequences = N > 1 request (do_sample): ONE prompt phase over the B prompts, N first
         tokens drawn from each prompt's logits, and a state of B * N rows for :meth:`generate_finish` — row b * N + i is sample i
         of prompt b, its draws counted by (seed, step, b * N + i) as the replicated batch's would be.
@@ -1787,14 +1849,18 @@ class GARModel:
         self._topk_planes(skey, st, (R, Smax - Sp if shared else Smax), top_k_lp, list(cands))
         self._arm_state(pst, left_pad, None, None, None)
         eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed)
+        self._arm_processing(skey, st, proc, eos_list, eos_on_device)
         to = _PickTargets.of(st, out_tokens)
         first_logits = []
         for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
                                                   feature_replay_video, video_frame_tokens):
             last = self._prefill(embeds, pst, Sp, b0)
-            lg = self._head(last, b1 - b0, pst, None).repeat_interleave(N, 0)      # the SAME logits for the N draws
+            lg = self._head(last, b1 - b0, pst, None)
             r0, r1 = _fanout_rows(b0, b1, N)
-            self._pick(lg, V, st, to.rows(r0, r1))      # the N rows of a prompt carry that prompt's top-k / candidate values at step 0
+            # the history of every row is empty at step 0: the N draws of a prompt share ONE processed row
+            self._process(lg, V, st, None)
+            lg = lg.repeat_interleave(N, 0)                                        # the SAME logits for the N draws
+            self._pick(lg, V, st, to.rows(r0, r1), process=False)   # the N rows of a prompt carry that prompt's top-k / candidate values at step 0
             if forced_tokens is not None:
                 st["cur"][r0:r1].copy_(forced_tokens[r0:r1, 0])
             if return_logits:
@@ -2023,7 +2089,8 @@ class GARModel:
         gkey = (skey, out_tokens.data_ptr(), out_tokens.stride(0), bool(st.get("sampling")), self.kv_cache_dtype,
                 st["fan"]["Kp"].data_ptr() if st.get("fan") else 0,         # (the prompt caches live in another state)
                 st.get("lp") is not None,                                   # return_logprobs: the step picks with the _lp launch
-                (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0))  # top_logprobs / candidates: one more launch, planes by (k, C)
+                (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0),  # top_logprobs / candidates: one more launch, planes by (k, C)
+                st.get("proc") is not None)                                 # logits_processing: one more launch in front of the pick
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

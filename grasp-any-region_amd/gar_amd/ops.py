@@ -715,6 +715,33 @@ def topk_lp(logits, V, step_dev, workspace, top_ids=None, top_lp=None, cand_ids=
                                         stream()), "gar_topk_lp")
 
 
+LOGITS_PROCESS_HEADER = 8            # gar_logits_process: words of the parameter block in front of its id lists
+LOGITS_PROCESS_WORDS = 4096          # capacity of the block a state keeps (int32 words): header + every list, see logits_processing.py
+
+
+def logits_process_max_vocab() -> int:
+    return int(lib().gar_logits_process_max_vocab())
+
+
+def logits_process(logits, V, out_tokens, step_dev, eos_ids, params):
+    """``gar_logits_process``: HF's repetition penalty / no-repeat n-gram / min-new-tokens / suppress / begin-suppress / bad-words
+    processors on the rows of ``logits`` [B, ld] in place, before the pick. The history of row b is ``out_tokens[b, :step_dev[0]]``
+    (int64 [B, cols], row-strided view allowed; ``step_dev`` None = step 0, ``out_tokens`` None = no history); ``eos_ids`` int64 [n]
+    (entries < 0 never match); ``params`` int32 device block laid out by :meth:`LogitsProcessing.pack`."""
+    B = logits.shape[0]
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() >= LOGITS_PROCESS_HEADER
+    assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
+    cols = stride = 0
+    if out_tokens is not None:
+        assert out_tokens.dtype == torch.int64 and out_tokens.dim() == 2 and out_tokens.shape[0] == B and \
+            (out_tokens.shape[1] <= 1 or out_tokens.stride(1) == 1)
+        cols, stride = out_tokens.shape[1], out_tokens.stride(0)
+    check(lib(logits.dtype).gar_logits_process(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), stride,
+                                               cols, ptr(step_dev), ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(),
+                                               ptr(params), params.numel(), stream()), "gar_logits_process")
+
+
 def input_check(input_ids, vocab: int, counts, n_rows: int, spans, span_len: int, has_box, flags, attn_mask=None):
     """device-side input checks of generate(validate=False): ORs INPUT_* bits into ``flags`` (int32 [1]). ``attn_mask``: bool /
     uint8 [B, S] generation mask; a row that is not left-padded sets INPUT_MASK_NOT_LEFT_PADDED."""

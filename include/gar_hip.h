@@ -533,6 +533,36 @@ int gar_topk_lp(int dtype, const void* logits, int64_t ld, int B, int V, int k, 
                 int64_t cand_row_stride, int64_t cand_step_stride, const int32_t* step_dev, void* workspace, gar_stream_t stream);
 int64_t gar_topk_lp_workspace(int B, int V, int k);
 
+/* ---- Logits processors of a step (GARModel.generate(logits_processing=...)) -------------------------------------------------------
+ * Additive: one entry point (and the constant it refuses by), GAR_ABI_VERSION stays 16. HF's RepetitionPenaltyLogitsProcessor,
+ * NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, MinNewTokensLengthLogitsProcessor, SuppressTokensLogitsProcessor and
+ * SuppressTokensAtBeginLogitsProcessor as the reference's call sees them — generate(inputs_embeds=...) without input_ids
+ * (modeling_gar.py:418-426), so the history of row b is its generated tokens only: out_tokens[b * out_stride + 0 .. t - 1] with
+ * t = step_dev[0] (NULL = 0) clamped to [0, out_cols]; out_tokens NULL = no history. Edits logits [B, ld] (f32 / the library's 16-bit
+ * type) in place, before gar_topk_lp / gar_sample / gar_argmax read them:
+ *   repetition penalty p > 0 (1 = off)  every DISTINCT history id: x < 0 ? x * p : x / p, in f32 on the stored value with a true
+ *                                       division, rounded to the storage type to nearest even — once, however often the id occurs;
+ *   no-repeat n-gram n >= 0 (0 = off)   t + 1 >= n: -inf at hist[j + n - 1] for every j <= t - n with hist[j .. j+n-2] == hist[t-n+1 .. t-1]
+ *                                       (n = 1: every history id);
+ *   min new tokens m                    t < m: -inf at every eos id (eos_ids int64 [n_eos], entries < 0 never match);
+ *   suppress / begin-suppress lists     -inf always / at t == 0 only;
+ *   bad words                           a one-token entry: -inf always; an entry of L > 1 tokens: -inf at its last token when L <= t (HF's
+ *                                       SequenceBiasLogitsProcessor ignores an entry longer than the context) and the history ends
+ *                                       with its first L - 1 tokens.
+ * params_dev: device int32 [params_words], read on every launch, so one captured graph serves any values:
+ *   [0] p as f32 bits  [1] n  [2] m  [3] n_suppress  [4] n_begin  [5] n_bad  [6] n_bad_tokens  [7] 0, then the suppress ids, the
+ *   begin-suppress ids, n_bad + 1 ascending offsets into the bad-word tokens (absent when n_bad = 0) and the bad-word tokens.
+ *   A block whose lists do not fit params_words names no list; params_words >= 8.
+ * Contract: ONE launch per step (one 1024-thread workgroup per row, two vocabulary bitmaps in LDS: V <= gar_logits_process_max_vocab()
+ * = 262144, any t); no allocation, no synchronisation, hipGraph-capturable, deterministic. Every vocabulary entry is computed from the
+ * value stored before the launch and written at most once, by one thread; columns V..ld-1 and every entry no processor names keep
+ * their bytes. An id outside [0, V) — in the history, the eos table or a list — is skipped and never dereferenced. -inf stays -inf;
+ * NaN logits are unspecified. Rows whose eos latch is set are processed like any other. */
+int gar_logits_process(int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens, int64_t out_stride,
+                       int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos, const int32_t* params_dev,
+                       int params_words, gar_stream_t stream);
+int gar_logits_process_max_vocab(void);
+
 #ifdef __cplusplus
 }
 #endif
