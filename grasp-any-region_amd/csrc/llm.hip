@@ -360,30 +360,38 @@ __device__ __forceinline__ unsigned int philox_first(unsigned int c0, unsigned i
     return c0;
 }
 
+// One row's request, as sample_row reads it: the warpers' parameters, the Philox key, the two counter words of the draw (the row's
+// step and its counter row) and the column of the token matrix the token is committed at. gar_sample / gar_sample_lp fill it from the
+// state's words (step = col = step_dev[0], counter row = row_offset + b), gar_sample_rows from row b's eight words.
+struct SmpReq {
+    float temperature, top_p;
+    int top_k;
+    unsigned int seed_lo, seed_hi, step, crow;
+    int col;
+};
+
+// The body of every sampling kernel: row b's token under rq, drawn by its 1024-thread workgroup (every thread of it calls this, with
+// the same rq) and committed at column rq.col.
 // LP (gar_sample_lp): the instantiation that also writes the drawn token's log-probabilities — raw = x[tok] - logsumexp(x[0:V]) over the
 // logits as stored, warped = z[tok] - max z - log Z2 over the kept set (the distribution the draw was taken from) — into planes laid
-// out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false (gar_sample) makes no such pass
-// and writes no plane.
+// out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false (gar_sample, gar_sample_rows)
+// makes no such pass and writes no plane.
 template <typename T, bool LP>
-__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V,
-                                                             int64_t* __restrict__ out_tokens, int64_t out_stride,
-                                                             const int32_t* __restrict__ step_dev, int64_t* __restrict__ cur_tokens,
-                                                             const float* __restrict__ params, const int64_t* __restrict__ seed_dev,
-                                                             const int64_t* __restrict__ eos_ids, int n_eos,
-                                                             int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
-                                                             int row_offset, float* __restrict__ lp_raw,
-                                                             float* __restrict__ lp_warped) {
+__device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int b, const SmpReq& rq,
+                                           int64_t* __restrict__ out_tokens, int64_t out_stride, int64_t* __restrict__ cur_tokens,
+                                           const int64_t* __restrict__ eos_ids, int n_eos, int32_t* __restrict__ finished,
+                                           int32_t* __restrict__ done_count, float* __restrict__ lp_raw,
+                                           float* __restrict__ lp_warped) {
     __shared__ float hist_f[SMP_WAVES][256];        // per-wave mass histograms (merged in wave order: deterministic)
     __shared__ int hist_i[256];
     __shared__ float red_f[SMP_WAVES];
     __shared__ float scan_f[SMP_THREADS];
     __shared__ unsigned int sh_u[4];
     __shared__ float sh_f[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const T* row = logits + (int64_t)b * ld;
-    const float temperature = params[0], top_p = params[1];
-    const int top_k = (int)params[2];
-    const float temp = temperature > 0.f ? temperature : 1.0f;             // (the host refuses temperature <= 0, as HF does)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float top_p = rq.top_p;
+    const int top_k = rq.top_k;
+    const float temp = rq.temperature > 0.f ? rq.temperature : 1.0f;       // (the host refuses temperature <= 0, as HF does)
     auto zof = [&](int i) { return DT<T>::ld(row + i) / temp; };
     auto block_sum = [&](float v) -> float {        // fixed shape: xor tree inside a wave, waves in order
         v = wave_sum(v);
@@ -515,12 +523,10 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
         red_f[tid] = t;
     }
     __syncthreads();
-    const int step = step_dev ? step_dev[0] : 0;
     if (tid == 0) {
         float Z2 = 0.f;
         for (int w = 0; w < SMP_WAVES; ++w) Z2 += red_f[w];
-        const unsigned long long seed = (unsigned long long)seed_dev[0];
-        const unsigned int r = philox_first((unsigned int)step, (unsigned int)(b + row_offset), 0u, 0u, (unsigned int)seed, (unsigned int)(seed >> 32));
+        const unsigned int r = philox_first(rq.step, rq.crow, 0u, 0u, rq.seed_lo, rq.seed_hi);
         const float u = (float)(r >> 8) * (1.0f / 16777216.0f);
         const float target = u * Z2;
         // segment, then chunk, then (below) element: running sums in the same fixed order
@@ -579,10 +585,66 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict
                 raw = (DT<T>::ld(row + tok) - xs) - logf(Zraw);
                 warped = (zof(tok) - mx) - logf(sh_f[2]);
             }
-            commit_token(b, tok, step, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
+            commit_token(b, tok, rq.col, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
                          LP ? lp_raw : nullptr, LP ? lp_warped : nullptr, raw, warped);
         }
     }
+}
+
+// gar_sample / gar_sample_lp: one request for all rows, out of the state's words
+template <typename T, bool LP>
+__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V,
+                                                             int64_t* __restrict__ out_tokens, int64_t out_stride,
+                                                             const int32_t* __restrict__ step_dev, int64_t* __restrict__ cur_tokens,
+                                                             const float* __restrict__ params, const int64_t* __restrict__ seed_dev,
+                                                             const int64_t* __restrict__ eos_ids, int n_eos,
+                                                             int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
+                                                             int row_offset, float* __restrict__ lp_raw,
+                                                             float* __restrict__ lp_warped) {
+    const int b = blockIdx.x;
+    const int step = step_dev ? step_dev[0] : 0;
+    const unsigned long long seed = (unsigned long long)seed_dev[0];
+    const SmpReq rq = {params[0], params[1], (int)params[2], (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)step,
+                       (unsigned int)(b + row_offset), step};
+    sample_row<T, LP>(logits + (int64_t)b * ld, V, b, rq, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
+                      lp_raw, lp_warped);
+}
+
+// gar_sample_rows: every row its own request, out of row_words [B][8] = {mode, temperature bits, top_p bits, top_k, seed low, seed
+// high, col0, counter row}. The column is the shared step_dev[0]; the row's step is its distance from col0. Mode 0 picks the largest
+// logit as stored in am_better's order (gar_argmax's token) with the row's own workgroup and draws nothing. The branch on the mode is
+// uniform over the workgroup (one word per row), so the barriers of either side are reached by all of its threads or by none.
+template <typename T>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(const T* __restrict__ logits, int64_t ld, int V,
+                                                                  int64_t* __restrict__ out_tokens, int64_t out_stride,
+                                                                  const int32_t* __restrict__ step_dev,
+                                                                  int64_t* __restrict__ cur_tokens,
+                                                                  const int32_t* __restrict__ row_words,
+                                                                  const int64_t* __restrict__ eos_ids, int n_eos,
+                                                                  int32_t* __restrict__ finished, int32_t* __restrict__ done_count) {
+    __shared__ float gv[SMP_WAVES];
+    __shared__ int gi[SMP_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const T* row = logits + (int64_t)b * ld;
+    const int32_t* w = row_words + (int64_t)b * 8;
+    const int col = step_dev ? step_dev[0] : 0;
+    if (w[0] == 0) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int i = tid; i < V; i += SMP_THREADS) am_better(bv, bi, DT<T>::ld(row + i), i);
+        wave_best(bv, bi);
+        if ((tid & 63) == 0) { gv[tid >> 6] = bv; gi[tid >> 6] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int k = 1; k < SMP_WAVES; ++k) am_better(bv, bi, gv[k], gi[k]);
+            commit_token(b, bi, col, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr, 0.f,
+                         0.f);
+        }
+        return;
+    }
+    const SmpReq rq = {__int_as_float(w[1]), __int_as_float(w[2]), w[3], (unsigned int)w[4], (unsigned int)w[5],
+                       (unsigned int)max(0, col - w[6]), (unsigned int)w[7], col};
+    sample_row<T, false>(row, V, b, rq, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr);
 }
 
 template <bool LP>
@@ -618,6 +680,22 @@ extern "C" int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, i
                              float* lp_raw, float* lp_warped, gar_stream_t stream) {
     return sample_launch<true>("sample_lp", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev,
                                eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped, stream);
+}
+
+extern "C" int gar_sample_rows(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                               const int32_t* step_dev, int64_t* cur_tokens, const int32_t* row_words, const int64_t* eos_ids,
+                               int n_eos, int32_t* finished, int32_t* done_count, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && row_words && B > 0 && V > 0 && (out_tokens || cur_tokens), "sample_rows: bad args");
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample_rows: eos_ids / finished");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((sample_rows_kernel<bf16_t>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens,
+                           out_stride, step_dev, cur_tokens, row_words, eos_ids, n_eos, finished, done_count);
+    else
+        hipLaunchKernelGGL((sample_rows_kernel<float>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens,
+                           out_stride, step_dev, cur_tokens, row_words, eos_ids, n_eos, finished, done_count);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
 }
 
 // workspace: pv | pi (gar_argmax), pv | pi | ps (gar_argmax_lp), AM_BLOCKS entries per row each

@@ -51,6 +51,12 @@ def base_parser(description, default_model, default_cache, default_images):
                     help="with --batch_size n > 1: keep n decode rows full instead of running static batches of n — a row whose "
                          "caption hits EOS is retired and the next queued item is admitted into it inside the running decode loop "
                          "(gar_amd/continuous.py), so a batch no longer pays for its longest caption in every row")
+    ap.add_argument("--do_sample", action="store_true",
+                    help="with --continuous: every item is a sampled request of its own (temperature / top-k / top-p on the device, "
+                         "item i under the Philox key --seed + i) instead of greedy search")
+    ap.add_argument("--temperature", type=float, default=None, help="with --do_sample (default: HF's 1.0)")
+    ap.add_argument("--top_k", type=int, default=None, help="with --do_sample (default: HF's 50; 0 = off)")
+    ap.add_argument("--top_p", type=float, default=None, help="with --do_sample (default: HF's 1.0 = off)")
     ap.add_argument("--kv_cache_dtype", choices=("auto", "fp8"), default="auto",
                     help="decode KV cache: auto = the model dtype; fp8 = OCP e4m3 with one scale per vector (16-bit models only)")
     ap.add_argument("--decode_weight_dtype", choices=("auto", "fp8"), default="auto",
@@ -90,6 +96,8 @@ def write_run_meta(path, args, model):
     record format). In bf16, batch size and pass sizes select kernels, so two runs of the same items can differ at near-tied
     greedy steps ("Batching and caption-level drift")."""
     meta = {"batch_size": int(getattr(args, "batch_size", 1) or 1), "continuous": bool(getattr(args, "continuous", False)),
+            **({"do_sample": True, "seed": args.seed, "temperature": args.temperature, "top_k": args.top_k, "top_p": args.top_p}
+               if getattr(args, "do_sample", False) else {}),
             "data_type": args.data_type,
             "max_num_tiles": args.max_num_tiles, "max_new_tokens": args.max_new_tokens,
             "synthetic_weights": bool(args.synthetic_weights), "host_preprocessing": bool(args.host_preprocessing),
@@ -202,8 +210,15 @@ class ContinuousRunner:
         from .continuous import ContinuousBatcher
         self.processor, self.skip = processor, skip_special_tokens
         tk = processor.tokenizer
+        # --do_sample: the options of every item's request, item i under the key --seed + i; without it the greedy loop as before
+        self.options = None
+        if getattr(args, "do_sample", False):
+            self.options = dict(do_sample=True, **{k: getattr(args, k) for k in ("temperature", "top_k", "top_p")
+                                                   if getattr(args, k, None) is not None})
+        self.seed0 = int(getattr(args, "seed", 0) or 0)
         self.cb = ContinuousBatcher(model, slots=max(2, int(args.batch_size)), max_new_tokens=args.max_new_tokens,
-                                    eos_token_id=tk.eos_token_id, poll_every=getattr(args, "poll_every", 8))
+                                    eos_token_id=tk.eos_token_id, poll_every=getattr(args, "poll_every", 8),
+                                    **({} if self.options is None else dict(sampling=True)))
         self.pending = {}
         self.results = []
         self.items = 0
@@ -217,7 +232,11 @@ class ContinuousRunner:
             self.results.append((idx, finish(text)))
 
     def add(self, idx, sample, finish):
-        self.pending[self.cb.submit(sample)] = (idx, finish)
+        if self.options is None:
+            ticket = self.cb.submit(sample)
+        else:
+            ticket = self.cb.submit(sample, seed=self.seed0 + self.items, **self.options)
+        self.pending[ticket] = (idx, finish)
         self.items += 1
         self.cb.pump()
         self._drain()
@@ -234,6 +253,8 @@ class ContinuousRunner:
 def make_runner(model, processor, args, skip_special_tokens):
     if getattr(args, "continuous", False) and int(getattr(args, "batch_size", 1) or 1) > 1:
         return ContinuousRunner(model, processor, args, skip_special_tokens)
+    if getattr(args, "do_sample", False):
+        raise SystemExit("--do_sample is implemented with --continuous --batch_size n > 1 only (the other loops are greedy)")
     return Batcher(model, processor, args, skip_special_tokens)
 
 

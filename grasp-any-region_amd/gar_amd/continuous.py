@@ -20,20 +20,68 @@ batch of B items runs max(len) steps in all B rows. Here one decode state of ``s
 * **re-basing.** ``P`` only grows; when a new row's whole life no longer fits under ``Smax`` the live rows are shifted down
   by the smallest ``left_pad`` among them (a rare bulk copy: every ``horizon`` steps).
 
-Greedy search only, like ``GARModel.generate``; a row's tokens are those of its own single-region ``generate`` (same kernels on
-the same data; in f32 identical, in bf16 up to the batch-size dependent kernel selection INTEGRATION.md describes)."""
+Greedy search by default; a row's tokens are those of its own single-region ``generate`` (same kernels on the same data; in
+f32 identical, in bf16 up to the batch-size dependent kernel selection INTEGRATION.md describes).
+
+* **per-request sampling** (``sampling=True``). The decode state then carries one request of eight int32 words per
+  row (:func:`pack_sample_row`): greedy or sampled, temperature / top-k / top-p, the Philox key, and ``col0`` — the column of
+  the token log the row's caption started at. The shared step counter is a column of that log, not any row's step;
+  ``gar_sample_rows`` reads the row's step as ``column - col0``, so one captured graph serves a batch in which every row samples,
+  or does not, under its own request, and a sampled ticket draws what ``generate(do_sample=True, seed=...)`` draws for it alone."""
 from __future__ import annotations
 
+import struct
 from collections import deque
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import hip
+from .ops import SAMPLE_ROW_WORDS        # gar_sample_rows: int32 words of one row's request (include/gar_hip.h)
 
 
 def _round_up(x, m):
     return (x + m - 1) // m * m
+
+
+def _i32(u: int) -> int:
+    """the low 32 bits of ``u`` as the int32 that holds them"""
+    u &= 0xffffffff
+    return u - (1 << 32) if u >= 1 << 31 else u
+
+
+def _f32_bits(x: float) -> int:
+    return _i32(struct.unpack("<I", struct.pack("<f", x))[0])
+
+
+def pack_sample_row(sampling, seed, col0: int, counter_row: int = 0, mode: Optional[int] = None) -> List[int]:
+    """The eight int32 words of one row's request as ``gar_sample_rows`` reads them: [mode, temperature bits, top_p bits, top_k,
+    seed low, seed high, col0, counter row]. ``sampling``: None for a greedy row (every word but ``col0`` is 0), else the
+    (temperature, top_p, top_k) of ``modeling_gar._sampling_options``; ``seed``: the Philox key, 0 <= seed < 2**63; ``col0``: the
+    token column of the row's step 0; ``counter_row``: Philox counter word 1 (0: the row draws what ``generate`` draws for it
+    alone). ``mode`` defaults to what ``sampling`` implies; anything but 0 / 1 is refused."""
+    if mode is None:
+        mode = 0 if sampling is None else 1
+    if isinstance(mode, bool) or mode not in (0, 1):
+        raise ValueError(f"mode has to be 0 (greedy) or 1 (sample), but is {mode!r}")
+    if mode != (0 if sampling is None else 1):
+        raise ValueError(f"mode {mode} does not go with sampling={sampling!r}")
+    col0, counter_row = int(col0), int(counter_row)
+    if not (-2 ** 31 <= col0 < 2 ** 31 and 0 <= counter_row < 2 ** 31):
+        raise ValueError(f"col0 {col0} / counter_row {counter_row} outside an int32")
+    if sampling is None:
+        return [0, 0, 0, 0, 0, 0, col0, 0]
+    temperature, top_p, top_k = float(sampling[0]), float(sampling[1]), sampling[2]
+    if not temperature > 0:
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+    if not 0 < top_p <= 1.0:
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+    if isinstance(top_k, bool) or int(top_k) != top_k or not 0 <= top_k < 2 ** 31:
+        raise ValueError(f"`top_k` has to be a non-negative integer (0 = off), but is {top_k!r}")
+    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 2 ** 63:
+        raise ValueError(f"seed has to be an integer in [0, 2**63), but is {seed!r}")
+    seed = int(seed)
+    return [1, _f32_bits(temperature), _f32_bits(top_p), int(top_k), _i32(seed), _i32(seed >> 32), col0, counter_row]
 
 
 class _Row:
@@ -56,7 +104,7 @@ class ContinuousBatcher:
     def __init__(self, model, slots: int, max_new_tokens: int = 1024, eos_token_id=None, poll_every: int = 8,
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
                  validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False,
-                 top_logprobs: int = 0, candidate_token_ids=None, logits_processing=None):
+                 top_logprobs: int = 0, candidate_token_ids=None, logits_processing=None, sampling: bool = False):
         if logits_processing is not None:
             # the processors read a row's history from columns 0..t-1 of the token matrix; this loop shifts that matrix per row
             # (_rebase), so a row's column is not its step: not threaded through here
@@ -91,6 +139,11 @@ class ContinuousBatcher:
         self.lookahead = self.B if lookahead is None else max(0, int(lookahead))
         self.horizon = max(256, 2 * self.max_new) if horizon is None else max(0, int(horizon))
         self.validate, self.use_graph = validate, use_graph
+        # per-request sampling: the decode state carries a request table (one row of words per decode row) and the step picks
+        # with gar_sample_rows. False: the state, the graph key and the launches of the greedy-only loop
+        self.sampling = bool(sampling)
+        self._requests: Dict[int, tuple] = {}                # ticket -> ((temperature, top_p, top_k), seed) of a sampled ticket
+        self.seeds: Dict[int, int] = {}                      # ticket -> Philox key, every sampled ticket
         self.smax_multiple = max(64, _round_up(int(smax_multiple), 64))      # cache rows come in buckets (graph / state reuse)
         self.queue: deque = deque()
         self.rows: List[Optional[_Row]] = [None] * self.B
@@ -106,7 +159,11 @@ class ContinuousBatcher:
                           live_row_steps=0)
 
     # ---- queue ------------------------------------------------------------------------------------------------------
-    def submit(self, sample: dict) -> int:
+    def submit(self, sample: dict, generation_config=None, seed: Optional[int] = None, **generate_kwargs) -> int:
+        """queue one region. The generation options are read as ``generate`` reads them (a GenerationConfig / dict with the
+        keyword arguments laid over it; HF's defaults, so ``top_k`` 50): ``do_sample=True`` — on a batcher built with
+        ``sampling=True`` — makes this ticket a sampled one under its own temperature / top_k / top_p and ``seed`` (None: drawn
+        as ``generate`` draws it; recorded in ``seeds[ticket]``). ``max_new_tokens`` and ``eos_token_id`` stay per batcher."""
         if int(sample["input_ids"].shape[0]) != 1:
             raise ValueError("ContinuousBatcher.submit takes one region per sample (input_ids [1, S])")
         if sample.get("top_logprobs") or sample.get("candidate_token_ids"):
@@ -116,10 +173,43 @@ class ContinuousBatcher:
             raise hip.GarError("ContinuousBatcher.submit: logits_processing is not implemented (call generate(logits_processing=...))")
         if sample.get("return_logprobs"):
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
+        request = self._read_options(generation_config, generate_kwargs, seed)
         t = self._next_ticket
         self._next_ticket += 1
+        if request is not None:
+            self._requests[t] = request
+            self.seeds[t] = request[1]
         self.queue.append((t, sample))
         return t
+
+    def _read_options(self, generation_config, generate_kwargs, seed):
+        """((temperature, top_p, top_k), seed) of a do_sample = True request, None for a greedy one; every option that is not
+        built raises as it does in generate"""
+        from .modeling_gar import _draw_seed, _num_return_sequences, _option_reader, _refuse_non_greedy, _sampling_options
+        get = _option_reader(generation_config, generate_kwargs)
+        if get is None:
+            return None
+        if _num_return_sequences(get) > 1:
+            raise hip.GarError(f"ContinuousBatcher.submit: num_return_sequences={get('num_return_sequences')} is not implemented "
+                               "(call generate(num_return_sequences=...), or submit the region once per caption)")
+        _refuse_non_greedy(get)
+        v = get("max_new_tokens")
+        if v is not None and int(v) != self.max_new:
+            raise hip.GarError(f"ContinuousBatcher.submit: max_new_tokens={v} differs from the batcher's {self.max_new} (it is set "
+                               "per batcher, not per request)")
+        v = get("eos_token_id")
+        if v is not None and sorted(int(e) for e in (v if isinstance(v, (list, tuple)) else [v])) != sorted(self.eos):
+            raise hip.GarError(f"ContinuousBatcher.submit: eos_token_id={v} differs from the batcher's {self.eos} (it is set per "
+                               "batcher, not per request)")
+        if not get("do_sample", False):
+            return None
+        if not self.sampling:
+            raise hip.GarError("ContinuousBatcher.submit: do_sample=True needs a batcher built with ContinuousBatcher(..., "
+                               "sampling=True)")
+        sampling = _sampling_options(get)
+        seed = _draw_seed() if seed is None else int(seed)
+        pack_sample_row(sampling, seed, 0)                   # (a seed outside [0, 2**63) is refused here, not at admission)
+        return sampling, seed
 
     def pump(self):
         """advance while more than ``lookahead`` regions are waiting (call after submit: keeps the queue bounded)"""
@@ -191,6 +281,8 @@ class ContinuousBatcher:
             idx = torch.tensor(retire, dtype=torch.int64, device=self.model.device)
             # a free row keeps replaying with the batch: hide its keys (one visible cache row) until it is admitted into again
             st["left_pad"].index_fill_(0, idx, self.Smax - 1)
+            if self.sampling:                # ... and its request: a free row is a greedy row that draws nothing
+                st["row_words"].index_fill_(0, idx, 0)
             for r in retire:
                 self.rows[r] = None
             self.stats["retired"] += len(retire)
@@ -256,8 +348,12 @@ class ContinuousBatcher:
             self.Smax = need
             self.skey, self.st = m._llm_state(self.B, self.Smax, self.DEC_SLOT)
             self.out_tokens = m._buf(self.skey, "out_tokens", (self.B, self.Smax), torch.int64, zero=True)
+            if self.sampling:
+                self.st["row_words"] = m._buf(self.skey, "row_words", (self.B, SAMPLE_ROW_WORDS), torch.int32, zero=True)
             self.graph = None
         st = self.st
+        if self.sampling:
+            st["row_words"].zero_()
         st["eos_ids"].fill_(-1)
         if self.eos:
             st["eos_ids"][:len(self.eos)].copy_(torch.tensor(self.eos, dtype=torch.int64, device=m.device))
@@ -305,6 +401,11 @@ class ContinuousBatcher:
             batch.update(feature_replay_video=True, video_frame_tokens=samples[0].get("video_frame_tokens"))
         # the ordinary prompt phase (planner passes, fused kernels) into the staging state; its head evaluates the stopping
         # criterion for the first token too (finished = 0 for a row whose first token is an eos id)
+        if self.sampling:
+            # the group's requests: a sampled ticket's first token is its step-0 draw with counter row 0, what generate() on that
+            # sample alone draws; in the staging state a caption starts at column 0
+            reqs = [self._requests.pop(t, (None, None)) for t, _ in group]
+            batch["_row_words"] = [pack_sample_row(sampling, seed, 0) for sampling, seed in reqs]
         pend = m.generate_begin(**batch, max_new_tokens=1, eos_token_id=self.eos or None, state_slot=self.STAGE_SLOT,
                                 validate=self.validate)
         if not self.validate:
@@ -325,6 +426,9 @@ class ContinuousBatcher:
         first = sg["cur"][:G]
         st["cur"].index_copy_(0, rows_t, first)
         st["left_pad"].index_copy_(0, rows_t, torch.tensor(offs, dtype=torch.int32, device=dev))
+        if self.sampling:                    # the rows' requests, their step 0 at the column the first token goes to
+            words = [pack_sample_row(sampling, seed, T - 1) for sampling, seed in reqs]
+            st["row_words"].index_copy_(0, rows_t, torch.tensor(words, dtype=torch.int32, device=dev))
         self.out_tokens[rows_t, T - 1] = first
         # first token already an eos id: latched at the column it was written to
         fin0 = torch.where(sg["finished"][:G] >= 0, torch.full((G,), T - 1, dtype=torch.int32, device=dev),
@@ -361,6 +465,8 @@ class ContinuousBatcher:
             for _, row in live:
                 row.start_col -= dT
         idx = torch.tensor([r for r, _ in live], dtype=torch.int64, device=self.model.device)
+        if dT > 0 and self.sampling:         # col0 moves with the token log (free rows hold zeros and draw nothing)
+            st["row_words"][:, 6].index_add_(0, idx, torch.full((len(live),), -dT, dtype=torch.int32, device=self.model.device))
         lp = torch.tensor([row.left_pad for _, row in live], dtype=torch.int32, device=self.model.device)
         st["left_pad"].index_copy_(0, idx, lp)
         # live rows are running (their latches are -1); free rows' latches are reset at admission

@@ -91,6 +91,7 @@ SIGNATURES = {
     "gar_argmax": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "gar_argmax_workspace": ([_i, _i], _i64),
     "gar_sample": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp], _i),
+    "gar_sample_rows": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "gar_argmax_lp": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "gar_argmax_lp_workspace": ([_i, _i], _i64),
     "gar_sample_lp": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -69,23 +69,26 @@ class GenerateOutput:
 class _PickTargets(NamedTuple):
     """where a pick (GARModel._pick) writes: the token matrix, the current tokens and the eos latches of its rows, the batch row of
     its first row (the Philox row counter of a draw), the (raw, warped) log-probability planes of a return_logprobs request or
-    None, and the planes of a top_logprobs / candidate_token_ids request (GARModel._topk_planes) or None."""
+    None, the planes of a top_logprobs / candidate_token_ids request (GARModel._topk_planes) or None, and the rows' own request
+    words (int32 [rows, 8], gar_sample_rows) of a state that carries them or None."""
     out_tokens: torch.Tensor
     cur: torch.Tensor
     finished: torch.Tensor
     row0: int
     lp: Optional[tuple]
     tk: Optional[dict]
+    row_words: Optional[torch.Tensor] = None
 
     @classmethod
     def of(cls, st, out_tokens) -> "_PickTargets":          # every row of a state
-        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"))
+        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"), st.get("row_words"))
 
     def rows(self, r0: int, r1: int) -> "_PickTargets":
         """cut to rows r0 .. r1 - 1: a prompt chunk's first-token head"""
         tk = self.tk and dict(self.tk, **{n: self.tk[n][r0:r1] for n in ("ids", "lp", "cand_lp") if self.tk[n] is not None})
         return _PickTargets(self.out_tokens[r0:r1], self.cur[r0:r1], self.finished[r0:r1], self.row0 + r0,
-                            self.lp and tuple(p[r0:r1] for p in self.lp), tk)
+                            self.lp and tuple(p[r0:r1] for p in self.lp), tk,
+                            None if self.row_words is None else self.row_words[r0:r1])
 
 
 def logprob_outputs(raw: torch.Tensor, warped: torch.Tensor, finished_at: Sequence[Optional[int]]):
@@ -295,6 +298,16 @@ def _sampling_options(get):
     if not 0 < top_p <= 1.0:
         raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
     return temperature, top_p, top_k
+
+
+def _draw_seed() -> int:
+    """the Philox key of a sampled request that names none. HF draws from torch's global generator: so does this key
+    (torch.manual_seed reproduces it)"""
+    seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        # identically seeded data-parallel ranks must not replay one stream on different regions
+        seed = (seed ^ (0x9E3779B97F4A7C15 * (torch.distributed.get_rank() + 1))) & (2 ** 62 - 1)
+    return seed
 
 
 def _round_up(x, m):
@@ -1397,7 +1410,9 @@ class GARModel:
         """the token of every row of ``logits`` into ``to``, by the request words of ``st``: the request's logits processors first
         (gar_logits_process, in place; ``process`` False: the caller ran them), then one gar_topk_lp when the request
         has top_logprobs / candidate_token_ids planes (it reads the logits only), then the draw (gar_sample) or the greedy pick
-        (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp)."""
+        (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp).
+        A state whose rows carry requests of their own (``to.row_words``: ContinuousBatcher(sampling=True)) picks every row with
+        gar_sample_rows instead."""
         B, tk, step = logits.shape[0], to.tk, st["counters"][2:3]
         key = ("head", B, st.get("slot", 0))
         if process:
@@ -1407,7 +1422,12 @@ class GARModel:
             ops.topk_lp(logits, V, step, ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"], cand_lp=tk["cand_lp"])
         raw, warped = to.lp or (None, None)
         latches = dict(eos_ids=st["eos_ids"], finished=to.finished, done_count=st["done_count"], logprobs=raw, logprobs_warped=warped)
-        if st.get("sampling"):
+        if to.row_words is not None:
+            if to.lp is not None or tk is not None or st.get("proc") is not None or st.get("sampling"):
+                raise hip.GarError("per-row sampling requests carry no log-probability planes and no logits processing")
+            ops.sample_rows(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, to.row_words, eos_ids=st["eos_ids"],
+                            finished=to.finished, done_count=st["done_count"])
+        elif st.get("sampling"):
             ops.sample(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_params"], st["sample_seed"],
                        row_offset=to.row0, **latches)
         else:                       # with planes one more f32 per partial block: a workspace of its own size
@@ -1655,7 +1675,7 @@ class GARModel:
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
                        top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None, logits_processing=None,
-                       **generate_kwargs) -> "_PendingGeneration":
+                       _row_words=None, **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
         the request; None draws one from torch's global generator).
@@ -1733,6 +1753,11 @@ class GARModel:
         self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
         eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
         self._arm_processing(skey, st, proc, eos_list, eos_on_device)
+        if _row_words is not None:      # ContinuousBatcher(sampling=True): the rows of this prompt phase pick under requests of their own
+            if len(_row_words) != B or sampling is not None:
+                raise hip.GarError("generate_begin: one request of eight words per row, and no do_sample of the call's own")
+            st["row_words"] = self._buf(skey, "row_words", (B, ops.SAMPLE_ROW_WORDS), torch.int32)
+            st["row_words"].copy_(self._upload([w for r in _row_words for w in r], torch.int32, cache=False).view(B, -1))
         to = _PickTargets.of(st, out_tokens)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
@@ -1808,11 +1833,8 @@ class GARModel:
             st["eos_ids"][:len(eos_list)].copy_(self._upload(eos_list, torch.int64))
         st["sampling"] = sampling is not None
         if sampling is not None:
-            if seed is None:          # HF draws from torch's global generator: so does the key of this request (torch.manual_seed reproduces it)
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
-                if torch.distributed.is_available() and torch.distributed.is_initialized():
-                    # identically seeded data-parallel ranks must not replay one stream on different regions
-                    seed = (seed ^ (0x9E3779B97F4A7C15 * (torch.distributed.get_rank() + 1))) & (2 ** 62 - 1)
+            if seed is None:
+                seed = _draw_seed()
             st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0], torch.float32))
             st["sample_seed"].copy_(self._upload([int(seed)], torch.int64, cache=False))
         return eos_list, eos_on_device
@@ -2090,7 +2112,8 @@ class GARModel:
                 st["fan"]["Kp"].data_ptr() if st.get("fan") else 0,         # (the prompt caches live in another state)
                 st.get("lp") is not None,                                   # return_logprobs: the step picks with the _lp launch
                 (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0),  # top_logprobs / candidates: one more launch, planes by (k, C)
-                st.get("proc") is not None)                                 # logits_processing: one more launch in front of the pick
+                st.get("proc") is not None,                                 # logits_processing: one more launch in front of the pick
+                st.get("row_words") is not None)                            # per-row requests: the step picks with gar_sample_rows
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

@@ -674,6 +674,23 @@ def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed
         check(lib(logits.dtype).gar_sample(*head, stream()), "gar_sample")
 
 
+SAMPLE_ROW_WORDS = 8                 # gar_sample_rows: int32 words of one row's request (continuous.pack_sample_row)
+
+
+def sample_rows(logits, V, out_tokens, out_stride, step_dev, cur_tokens, row_words, eos_ids=None, finished=None, done_count=None):
+    """``gar_sample_rows``: every row of ``logits`` picks its token under its own request, ``row_words`` int32 [B, 8] (device):
+    mode (0 greedy / 1 sample), temperature and top_p as f32 bits, top_k, the Philox key's low / high word, ``col0`` — the token
+    column of the row's step 0 — and the counter row. A sampled row draws what :func:`sample` draws on it alone at step
+    ``step_dev[0] - col0`` with ``row_offset`` = its counter row; a greedy row gets :func:`argmax`'s token. Token placement and eos
+    latches as :func:`argmax`, at the shared column ``step_dev[0]``."""
+    B = logits.shape[0]
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    assert row_words.dtype == torch.int32 and row_words.is_contiguous() and tuple(row_words.shape) == (B, SAMPLE_ROW_WORDS)
+    check(lib(logits.dtype).gar_sample_rows(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
+                                            ptr(step_dev), ptr(cur_tokens), ptr(row_words),
+                                            *_latches(B, eos_ids, finished, done_count), stream()), "gar_sample_rows")
+
+
 def argmax_workspace(B, V) -> int:
     return int(lib().gar_argmax_workspace(B, V))
 

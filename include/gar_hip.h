@@ -563,6 +563,26 @@ int gar_logits_process(int dtype, void* logits, int64_t ld, int B, int V, const 
                        int params_words, gar_stream_t stream);
 int gar_logits_process_max_vocab(void);
 
+/* ---- Per-row requests in one batch (ContinuousBatcher(sampling=True)) ----------------------------------------------------------------
+ * Additive: one entry point beside gar_sample / gar_argmax, whose signatures and results stand, so GAR_ABI_VERSION stays 16. The rows
+ * of one launch belong to different requests: row b picks its token under row_words[b] — device int32 [B][8], read on every launch,
+ * so one captured graph serves any values:
+ *   [0] mode: 0 = greedy, 1 = sample (the kernel takes any non-zero word as 1)   [1] temperature as f32 bits (<= 0 is read as 1.0)
+ *   [2] top_p as f32 bits   [3] top_k (0 or >= V = off)   [4] / [5] the Philox key's low / high 32 bits
+ *   [6] col0: the column of the token matrix at which this row's step 0 was written   [7] counter row: Philox counter word 1.
+ * With c = step_dev[0] (NULL = 0) the row's own step is t = max(0, c - col0).
+ *   mode 1  gar_sample's token for this row of logits under (temperature, top_p, top_k), key = seed, counter = (t, word 7, 0, 0): what
+ *           gar_sample returns on the row alone with step = t and row_offset = word 7, bit for bit — one kernel body forms both;
+ *   mode 0  no draw, the temperature is not read: the largest logit as stored, equal values by ascending index — gar_argmax's token,
+ *           found by the row's own workgroup.
+ * Token placement and the eos latches are gar_argmax's at the SHARED column c: out_tokens[b * out_stride + c], cur_tokens[b],
+ * finished[b] = c at the row's first eos id, done_count. One 1024-thread workgroup per row; columns V..ld-1 are never read, and no
+ * value of the words makes the kernel read outside the row. No workspace, no allocation, no synchronisation, hipGraph-capturable,
+ * deterministic. */
+int gar_sample_rows(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                    const int32_t* step_dev, int64_t* cur_tokens, const int32_t* row_words /* device int32 [B][8] */,
+                    const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, gar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
