@@ -37,6 +37,11 @@ def base_parser(description):
     ap.add_argument("--temperature", type=float, default=None, help="sampling temperature (implies sampling)")
     ap.add_argument("--top_p", type=float, default=None, help="nucleus sampling (implies sampling)")
     ap.add_argument("--top_k", type=int, default=None, help="top-k sampling (implies sampling)")
+    ap.add_argument("--min_p", type=float, default=None,
+                    help="drop tokens less likely than min_p x the most likely one (implies sampling)")
+    ap.add_argument("--typical_p", type=float, default=None, help="locally typical sampling mass (implies sampling)")
+    ap.add_argument("--epsilon_cutoff", type=float, default=None, help="drop tokens of probability < epsilon (implies sampling)")
+    ap.add_argument("--eta_cutoff", type=float, default=None, help="entropy-dependent probability cutoff (implies sampling)")
     ap.add_argument("--top_logprobs", type=int, default=0, metavar="K",
                     help="print, under each output and per generated token, the K most likely tokens as decoded-token:probability "
                          "(raw softmax of the step's logits, also when sampling; K <= 32)")
@@ -76,14 +81,27 @@ def generation_config(args, processor):
               pad_token_id=processor.tokenizer.pad_token_id)
     knobs = {k: getattr(args, k, None) for k in ("temperature", "top_p", "top_k")}
     n = getattr(args, "num_return_sequences", 1)
-    if n != 1 or any(v is not None for v in knobs.values()):           # the reference CLI is greedy: sampling only when asked for
+    # the reference CLI is greedy: sampling only when asked for
+    if n != 1 or any(v is not None for v in knobs.values()) or any(v is not None for v in _warper_args(args).values()):
         gc.update(do_sample=True, num_return_sequences=n, **{k: v for k, v in knobs.items() if v is not None})
     return gc
 
 
+WARPER_ARGS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+
+
+def _warper_args(args):
+    return {k: getattr(args, k, None) for k in WARPER_ARGS}
+
+
 def sampling_kwargs(args, gc):
-    """generate() keywords that go with :func:`generation_config`: the request's Philox key when it samples"""
-    return dict(seed=args.seed) if gc.get("do_sample") else {}
+    """generate() keywords that go with :func:`generation_config`: the request's Philox key when it samples, and the
+    sampling_warpers parameter when one of --min_p / --typical_p / --epsilon_cutoff / --eta_cutoff acts"""
+    if not gc.get("do_sample"):
+        return {}
+    from gar_amd import SamplingWarpers
+    sw = SamplingWarpers(**_warper_args(args))
+    return dict(seed=args.seed) if sw.neutral else dict(seed=args.seed, sampling_warpers=sw)
 
 
 def logits_processing_kwargs(args):

@@ -6,7 +6,8 @@
 //   argmax         greedy sampling with first-index tie break; writes into the device-side token matrix
 //   sample         do_sample = True: temperature / top-k / top-p warpers + one Philox draw per row and step
 //                  (both with an LP instantiation that also writes the chosen token's log-probability;
-//                  one epilogue, commit_token, commits the token)
+//                  one epilogue, commit_token, commits the token; sample_ext: the same body with HF's min_p / typical_p /
+//                  epsilon / eta cutoff warpers between top-p and the draw)
 //   topk_lp        the k most likely tokens of a step and the log-probabilities of given token ids
 #include "common.h"
 
@@ -368,7 +369,12 @@ struct SmpReq {
     int top_k;
     unsigned int seed_lo, seed_hi, step, crow;
     int col;
+    float min_p = 0.f, typical_p = 1.f, epsilon = 0.f, eta = 0.f;       // EXT only (gar_sample_ext): 0 / 1 / 0 / 0 = off
+    int32_t* n_kept = nullptr;                                          // EXT only: the size of the final kept set, [B] or NULL
 };
+
+// The key floor of "keep z >= thr": -0 sorts below +0 in smp_key's order, so a threshold of either zero takes the lower key
+__device__ __forceinline__ unsigned int smp_floor_key(float thr) { return smp_key(thr == 0.f ? -0.f : thr); }
 
 // The body of every sampling kernel: row b's token under rq, drawn by its 1024-thread workgroup (every thread of it calls this, with
 // the same rq) and committed at column rq.col.
@@ -376,7 +382,18 @@ struct SmpReq {
 // logits as stored, warped = z[tok] - max z - log Z2 over the kept set (the distribution the draw was taken from) — into planes laid
 // out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false (gar_sample, gar_sample_rows)
 // makes no such pass and writes no plane.
-template <typename T, bool LP>
+// EXT (gar_sample_ext): HF's four further warpers between top-p and the draw, in GenerationMixin._get_logits_processor's order, each
+// over the set the stage before it left (p = e / Z of that set, e = exp(z - mx), mx the ROW maximum: a common shift cancels):
+//   min_p     keep p >= min_p x max p. The row maximum is in the set, so this is e >= min_p: a key floor at mx + log(min_p), no pass;
+//   typical_p s = |(z - mx) - mean|, mean = sum e (z - mx) / Z (the entropy is log Z - mean); keep s <= s_cut, s_cut the largest s whose
+//             strictly smaller s hold less than typical_p of the mass: one pass for (Z, mean), then top-p's four-level descent
+//             run ASCENDING over the bits of s (s >= 0: its bits order like its value). It may remove the maximum;
+//   epsilon   keep p >= epsilon, and the set's maximum: one mass pass, a key floor at min(mx + log(epsilon Z), max of the set);
+//   eta       the same with eta' = min(eta, sqrt(eta) exp(-H)), H the set's entropy: one mass + entropy pass.
+// The kept set is ONE predicate, kept(z): the key floor key_lo and, when typical_p acted, s <= typ_cut recomputed from the saved
+// (typ_mean, typ_cut) — every pass after a stage and the draw evaluate exactly it. A stage that is off adds no pass and no barrier;
+// with all four off the instantiation computes gar_sample's token and planes bit for bit. EXT = false compiles none of it.
+template <typename T, bool LP, bool EXT = false>
 __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int b, const SmpReq& rq,
                                            int64_t* __restrict__ out_tokens, int64_t out_stride, int64_t* __restrict__ cur_tokens,
                                            const int64_t* __restrict__ eos_ids, int n_eos, int32_t* __restrict__ finished,
@@ -507,15 +524,136 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
         }
         key_lo = max(key_lo, prefix);
     }
+    // ---- EXT: min_p, typical_p, epsilon, eta (see above). typ_on / typ_mean / typ_cut and key_lo are uniform over the workgroup
+    bool typ_on = false;
+    float typ_mean = 0.f, typ_cut = 0.f;
+    auto kept = [&](float z) -> bool {
+        if constexpr (EXT) return smp_key(z) >= key_lo && (!typ_on || fabsf((z - mx) - typ_mean) <= typ_cut);
+        else return smp_key(z) >= key_lo;
+    };
+    if constexpr (EXT) {
+        auto mass_and_mean = [&](float& Z, float& S) {     // Z = sum e, S = sum e (z - mx) over the kept set (e = 0: no term, never 0 x inf)
+            float pz = 0.f, ps = 0.f;
+            for (int i = tid; i < V; i += SMP_THREADS) {
+                const float z = zof(i);
+                if (kept(z)) {
+                    const float e = __expf(z - mx);
+                    pz += e;
+                    ps += e > 0.f ? e * (z - mx) : 0.f;
+                }
+            }
+            Z = block_sum(pz);
+            S = block_sum(ps);
+        };
+        if (rq.min_p > 0.f) key_lo = max(key_lo, smp_floor_key(mx + logf(rq.min_p)));
+        if (rq.typical_p > 0.f && rq.typical_p < 1.0f) {
+            float Zt, St;
+            mass_and_mean(Zt, St);
+            const float mean = St / Zt, lim = rq.typical_p * Zt;
+            unsigned int prefix = 0u;
+            float below = 0.f;
+            for (int level = 3; level >= 0; --level) {
+                const int sh = level * 8;
+                const unsigned int pmask = level == 3 ? 0u : (0xffffffffu << (sh + 8));
+                for (int i = tid; i < SMP_WAVES * 256; i += SMP_THREADS) (&hist_f[0][0])[i] = 0.f;
+                for (int i = tid; i < 256; i += SMP_THREADS) hist_i[i] = 0;
+                __syncthreads();
+                for (int i0 = wave * 64; i0 < V; i0 += SMP_THREADS) {
+                    const int i = i0 + lane;
+                    if (i < V) {
+                        const float z = zof(i);
+                        const unsigned int k = __float_as_uint(fabsf((z - mx) - mean));
+                        if (kept(z) && (k & pmask) == prefix) {         // (typ_on is still false: the set min_p left)
+                            atomicAdd(&hist_f[wave][(k >> sh) & 255u], __expf(z - mx));
+                            atomicAdd(&hist_i[(k >> sh) & 255u], 1);
+                        }
+                    }
+                }
+                __syncthreads();
+                if (tid < 256) {
+                    float t = 0.f;
+                    for (int w = 0; w < SMP_WAVES; ++w) t += hist_f[w][tid];
+                    scan_f[tid] = t;
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    // highest non-empty bucket whose mass-below is still < lim (the lowest one always qualifies: HF keeps one token)
+                    int bsel = -1;
+                    float run = below, run_sel = below;
+                    for (int q = 0; q < 256; ++q) {
+                        if (hist_i[q] > 0) {
+                            if (run < lim || bsel < 0) { bsel = q; run_sel = run; }
+                            else break;
+                        }
+                        run += scan_f[q];
+                    }
+                    sh_u[0] = (unsigned int)max(bsel, 0);
+                    sh_f[0] = run_sel;
+                }
+                __syncthreads();
+                prefix |= sh_u[0] << sh;
+                below = sh_f[0];
+                __syncthreads();
+            }
+            typ_on = true;
+            typ_mean = mean;
+            typ_cut = __uint_as_float(prefix);
+        }
+        const bool eps_on = rq.epsilon > 0.f && rq.epsilon < 1.0f, eta_on = rq.eta > 0.f && rq.eta < 1.0f;
+        float m2 = mx;                              // the maximum of the set: the row's unless typical_p removed it
+        if (typ_on && (eps_on || eta_on)) {
+            m2 = -INFINITY;
+            for (int i = tid; i < V; i += SMP_THREADS) {
+                const float z = zof(i);
+                if (kept(z)) m2 = fmaxf(m2, z);
+            }
+            m2 = wave_max(m2);
+            __syncthreads();
+            if (lane == 0) red_f[wave] = m2;
+            __syncthreads();
+            m2 = red_f[0];
+            for (int w = 1; w < SMP_WAVES; ++w) m2 = fmaxf(m2, red_f[w]);
+        }
+        if (eps_on) {
+            float pz = 0.f;
+            for (int i = tid; i < V; i += SMP_THREADS) {
+                const float z = zof(i);
+                pz += kept(z) ? __expf(z - mx) : 0.f;
+            }
+            const float Ze = block_sum(pz);
+            key_lo = max(key_lo, smp_floor_key(fminf(mx + logf(rq.epsilon * Ze), m2)));
+        }
+        if (eta_on) {
+            float Zh, Sh;
+            mass_and_mean(Zh, Sh);
+            const float H = logf(Zh) - Sh / Zh;
+            const float cut = fminf(rq.eta, sqrtf(rq.eta) * __expf(-H));
+            key_lo = max(key_lo, smp_floor_key(fminf(mx + logf(cut * Zh), m2)));
+        }
+        if (rq.n_kept) {
+            if (tid == 0) hist_i[0] = 0;
+            __syncthreads();
+        }
+    }
     // ---- draw: contiguous chunks of the vocabulary per thread, exclusive scan of the chunk sums, the owning thread walks its chunk
     const int per = (V + SMP_THREADS - 1) / SMP_THREADS;
     const int c0 = tid * per, c1 = min(V, c0 + per);
     float csum = 0.f;
+    int ckept = 0;
     for (int i = c0; i < c1; ++i) {
         const float z = zof(i);
-        csum += smp_key(z) >= key_lo ? __expf(z - mx) : 0.f;
+        const bool k = kept(z);
+        csum += k ? __expf(z - mx) : 0.f;
+        if constexpr (EXT) ckept += (k && z > -INFINITY) ? 1 : 0;
     }
     scan_f[tid] = csum;
+    if constexpr (EXT) {
+        if (rq.n_kept) {                            // integer adds: any order gives the same count
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) ckept += __shfl_xor(ckept, o, 64);
+            if (lane == 0 && ckept) atomicAdd(&hist_i[0], ckept);
+        }
+    }
     __syncthreads();
     if (tid < SMP_WAVES) {                          // 16 segment sums of 64 chunks each, sequential: a fixed order
         float t = 0.f;
@@ -559,6 +697,9 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
         sh_f[0] = run;
         sh_f[1] = target;
         if constexpr (LP) sh_f[2] = Z2;
+        if constexpr (EXT) {
+            if (rq.n_kept) rq.n_kept[b] = hist_i[0];
+        }
     }
     __syncthreads();
     if (tid == (int)sh_u[0] || (!sh_u[1] && tid == 0)) {
@@ -568,7 +709,7 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
             const float target = sh_f[1];
             for (int i = c0; i < c1; ++i) {
                 const float z = zof(i);
-                if (smp_key(z) >= key_lo) {
+                if (kept(z)) {
                     run += __expf(z - mx);
                     tok = i;                               // the last kept index seen: the answer if rounding leaves run == target
                     if (run > target) break;
@@ -577,7 +718,7 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
         }
         if (tok < 0 && tid == 0) {                         // nothing exceeded the target (u x total rounded up to the total): last kept index
             for (int i = V - 1; i >= 0; --i)
-                if (smp_key(zof(i)) >= key_lo) { tok = i; break; }
+                if (kept(zof(i))) { tok = i; break; }
         }
         if (tok >= 0) {                                    // every exit above ends here with its tok: one place commits it
             float raw = 0.f, warped = 0.f;
@@ -680,6 +821,58 @@ extern "C" int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, i
                              float* lp_raw, float* lp_warped, gar_stream_t stream) {
     return sample_launch<true>("sample_lp", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev,
                                eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped, stream);
+}
+
+// gar_sample_ext: gar_sample / gar_sample_lp with params [8] = {temperature, top_p, top_k, 0, min_p, typical_p, epsilon_cutoff,
+// eta_cutoff} and the nullable n_kept [B]; the host picks LP by the planes
+template <typename T, bool LP>
+__global__ __launch_bounds__(SMP_THREADS) void sample_ext_kernel(const T* __restrict__ logits, int64_t ld, int V,
+                                                                 int64_t* __restrict__ out_tokens, int64_t out_stride,
+                                                                 const int32_t* __restrict__ step_dev, int64_t* __restrict__ cur_tokens,
+                                                                 const float* __restrict__ params, const int64_t* __restrict__ seed_dev,
+                                                                 const int64_t* __restrict__ eos_ids, int n_eos,
+                                                                 int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
+                                                                 int row_offset, float* __restrict__ lp_raw,
+                                                                 float* __restrict__ lp_warped, int32_t* __restrict__ n_kept) {
+    const int b = blockIdx.x;
+    const int step = step_dev ? step_dev[0] : 0;
+    const unsigned long long seed = (unsigned long long)seed_dev[0];
+    const SmpReq rq = {params[0], params[1], (int)params[2], (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)step,
+                       (unsigned int)(b + row_offset), step, params[4], params[5], params[6], params[7], n_kept};
+    sample_row<T, LP, true>(logits + (int64_t)b * ld, V, b, rq, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished,
+                            done_count, lp_raw, lp_warped);
+}
+
+template <bool LP>
+static void sample_ext_launch(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                              const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
+                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset, float* lp_raw,
+                              float* lp_warped, int32_t* n_kept, hipStream_t s) {
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((sample_ext_kernel<bf16_t, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens,
+                           out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset,
+                           lp_raw, lp_warped, n_kept);
+    else
+        hipLaunchKernelGGL((sample_ext_kernel<float, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens,
+                           out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset,
+                           lp_raw, lp_warped, n_kept);
+}
+
+extern "C" int gar_sample_ext(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                              const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
+                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
+                              float* lp_raw, float* lp_warped, int32_t* n_kept, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0,
+                  "sample_ext: bad args");
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample_ext: eos_ids / finished");
+    if (lp_raw || lp_warped)
+        sample_ext_launch<true>(dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids,
+                                n_eos, finished, done_count, row_offset, lp_raw, lp_warped, n_kept, (hipStream_t)stream);
+    else
+        sample_ext_launch<false>(dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids,
+                                 n_eos, finished, done_count, row_offset, nullptr, nullptr, n_kept, (hipStream_t)stream);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
 }
 
 extern "C" int gar_sample_rows(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,

@@ -6,5 +6,6 @@ PyTorch fallback: importing :mod:`gar_amd.hip` without the built library raises.
 """
 from .configuration_gar import GARConfig, PerceptionLMConfig, TextConfig, VisionConfig  # noqa: F401
 from .logits_processing import LogitsProcessing  # noqa: F401
+from .sampling_warpers import SamplingWarpers  # noqa: F401
 
-__all__ = ["GARConfig", "PerceptionLMConfig", "TextConfig", "VisionConfig", "LogitsProcessing"]
+__all__ = ["GARConfig", "PerceptionLMConfig", "TextConfig", "VisionConfig", "LogitsProcessing", "SamplingWarpers"]

@@ -104,7 +104,12 @@ class ContinuousBatcher:
     def __init__(self, model, slots: int, max_new_tokens: int = 1024, eos_token_id=None, poll_every: int = 8,
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
                  validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False,
-                 top_logprobs: int = 0, candidate_token_ids=None, logits_processing=None, sampling: bool = False):
+                 top_logprobs: int = 0, candidate_token_ids=None, logits_processing=None, sampling: bool = False,
+                 sampling_warpers=None):
+        if sampling_warpers is not None:
+            # a row's request is eight words (gar_sample_rows, SAMPLE_ROW_WORDS) and all eight are taken: the four warpers have no
+            # place in it yet
+            raise hip.GarError("ContinuousBatcher: sampling_warpers is not implemented (call generate(sampling_warpers=...))")
         if logits_processing is not None:
             # the processors read a row's history from columns 0..t-1 of the token matrix; this loop shifts that matrix per row
             # (_rebase), so a row's column is not its step: not threaded through here
@@ -159,7 +164,8 @@ class ContinuousBatcher:
                           live_row_steps=0)
 
     # ---- queue ------------------------------------------------------------------------------------------------------
-    def submit(self, sample: dict, generation_config=None, seed: Optional[int] = None, **generate_kwargs) -> int:
+    def submit(self, sample: dict, generation_config=None, seed: Optional[int] = None, sampling_warpers=None,
+               **generate_kwargs) -> int:
         """queue one region. The generation options are read as ``generate`` reads them (a GenerationConfig / dict with the
         keyword arguments laid over it; HF's defaults, so ``top_k`` 50): ``do_sample=True`` — on a batcher built with
         ``sampling=True`` — makes this ticket a sampled one under its own temperature / top_k / top_p and ``seed`` (None: drawn
@@ -171,6 +177,8 @@ class ContinuousBatcher:
                                "generate(top_logprobs=..., candidate_token_ids=...))")
         if sample.get("logits_processing") is not None:
             raise hip.GarError("ContinuousBatcher.submit: logits_processing is not implemented (call generate(logits_processing=...))")
+        if sampling_warpers is not None or sample.get("sampling_warpers") is not None:
+            raise hip.GarError("ContinuousBatcher.submit: sampling_warpers is not implemented (call generate(sampling_warpers=...))")
         if sample.get("return_logprobs"):
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
         request = self._read_options(generation_config, generate_kwargs, seed)

@@ -95,6 +95,7 @@ SIGNATURES = {
     "gar_argmax_lp": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "gar_argmax_lp_workspace": ([_i, _i], _i64),
     "gar_sample_lp": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
+    "gar_sample_ext": ([_i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "gar_topk_lp": ([_i, _vp, _i64, _i, _i, _i, _vp, _vp, _i64, _i64, _vp, _i, _vp, _i64, _i64, _vp, _vp, _vp], _i),
     "gar_topk_lp_workspace": ([_i, _i, _i], _i64),
     "gar_logits_process": ([_i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _vp], _i),

@@ -23,6 +23,7 @@ import torch
 from . import hip, ops
 from .configuration_gar import GARConfig
 from .logits_processing import LogitsProcessing, _Refused as _ProcessingRefused
+from .sampling_warpers import SamplingWarpers
 from .planner import plan_chunks
 from .weights import LM, PJ, VT, check_weights, load_weights, normalize_checkpoint, synthetic_weights
 
@@ -279,12 +280,14 @@ def _refuse_non_greedy(get):
 def _sampling_options(get):
     """(temperature, top_p, top_k) of a do_sample = True request, with HF's defaults (GenerationConfig: temperature 1.0, top_k 50,
     top_p 1.0) and HF's argument checks (TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper). The warpers that are not
-    built (min_p, typical_p, epsilon / eta cutoff) are refused when they would act."""
+    read from the options (min_p, typical_p, epsilon / eta cutoff) are refused when they would act: they come under
+    generate(sampling_warpers=...), DESIGN 7.9."""
     for name, neutral in (("min_p", (None, 0, 0.0)), ("typical_p", (None, 1, 1.0)), ("epsilon_cutoff", (None, 0, 0.0)),
                           ("eta_cutoff", (None, 0, 0.0))):
         v = get(name)
         if not any((v is n) or (n is not None and not isinstance(v, bool) and v == n) for n in neutral):
-            raise hip.GarError(f"sampling option {name}={v!r} is not implemented (temperature, top_k and top_p are)")
+            raise hip.GarError(f"sampling option {name}={v!r} is not implemented (temperature, top_k and top_p are) — pass "
+                               "generate(sampling_warpers=SamplingWarpers(...)) instead")
     temperature = get("temperature", 1.0)
     temperature = 1.0 if temperature is None else float(temperature)
     if not temperature > 0:
@@ -1200,6 +1203,8 @@ class GARModel:
             # do_sample = True (gar_sample): [temperature, top_p, top_k] and the Philox key of the request, read by the captured step
             sample_params=self._buf(key, "sample_params", (4,), torch.float32, zero=True),
             sample_seed=self._buf(key, "sample_seed", (1,), torch.int64, zero=True),
+            # sampling_warpers (gar_sample_ext): sample_params' four floats, then [min_p, typical_p, epsilon_cutoff, eta_cutoff]
+            sample_ext_params=self._buf(key, "sample_ext_params", (ops.SAMPLE_EXT_PARAMS,), torch.float32, zero=True),
             sampling=False,
             slot=slot,
         )
@@ -1410,7 +1415,8 @@ class GARModel:
         """the token of every row of ``logits`` into ``to``, by the request words of ``st``: the request's logits processors first
         (gar_logits_process, in place; ``process`` False: the caller ran them), then one gar_topk_lp when the request
         has top_logprobs / candidate_token_ids planes (it reads the logits only), then the draw (gar_sample) or the greedy pick
-        (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp).
+        (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp); a
+        sampled request with sampling_warpers draws with gar_sample_ext in gar_sample's place.
         A state whose rows carry requests of their own (``to.row_words``: ContinuousBatcher(sampling=True)) picks every row with
         gar_sample_rows instead."""
         B, tk, step = logits.shape[0], to.tk, st["counters"][2:3]
@@ -1427,6 +1433,9 @@ class GARModel:
                 raise hip.GarError("per-row sampling requests carry no log-probability planes and no logits processing")
             ops.sample_rows(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, to.row_words, eos_ids=st["eos_ids"],
                             finished=to.finished, done_count=st["done_count"])
+        elif st.get("sampling") and st.get("warpers"):          # sampling_warpers: the same pick through gar_sample_ext
+            ops.sample_ext(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_ext_params"], st["sample_seed"],
+                           row_offset=to.row0, **latches)
         elif st.get("sampling"):
             ops.sample(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_params"], st["sample_seed"],
                        row_offset=to.row0, **latches)
@@ -1675,7 +1684,7 @@ class GARModel:
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
                        top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None, logits_processing=None,
-                       _row_words=None, **generate_kwargs) -> "_PendingGeneration":
+                       sampling_warpers=None, _row_words=None, **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
         the request; None draws one from torch's global generator).
@@ -1707,7 +1716,16 @@ class GARModel:
         scanned. ``return_logits=True`` then returns the processed scores (HF's ``scores``). None or all-neutral values: the path
         and the launches of a call without it. Refused with ``GarError``: together with ``forced_tokens`` (the fed history would
         differ from ``sequences``), and with ``return_logprobs`` / ``top_logprobs`` / ``candidate_token_ids`` (defined over the raw
-        logits). The GenerationConfig fields of the same names stay refused."""
+        logits). The GenerationConfig fields of the same names stay refused.
+
+        ``sampling_warpers``: a :class:`SamplingWarpers` (or a dict of its fields) — ``min_p``, ``typical_p``, ``epsilon_cutoff``,
+        ``eta_cutoff``: HF's four further warpers, applied on the device in HF's order after temperature / top-k / top-p and before
+        the draw, each over the tokens the stage before it left. Needs ``do_sample=True`` (``ValueError`` otherwise).
+        ``token_logprobs_warped`` is then the drawn token's log-probability under the final kept set. None or all-neutral values:
+        the path, the launches and the captured graph of a call without it. The GenerationConfig fields of the same names stay
+        refused."""
+        warpers = SamplingWarpers.coerce(sampling_warpers)
+        warpers = None if warpers.neutral else warpers
         proc = LogitsProcessing.coerce(logits_processing)
         proc = None if proc.neutral else proc
         if proc is not None:
@@ -1734,6 +1752,11 @@ class GARModel:
             pad_token_id = get("pad_token_id")
         else:
             pad_token_id = None
+        if warpers is not None and sampling is None:
+            raise ValueError("sampling_warpers acts on a sampled request only: pass do_sample=True (greedy search draws nothing "
+                             "to warp)")
+        if warpers is not None and _row_words is not None:
+            raise hip.GarError("generate_begin: per-row requests carry no sampling_warpers")
         max_new_tokens = int(max_new_tokens or 64)
         cfg = self.config
         B, S = input_ids.shape
@@ -1742,7 +1765,7 @@ class GARModel:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
                                                return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
-                                               state_slot, return_logprobs, top_k_lp, cands, proc)
+                                               state_slot, return_logprobs, top_k_lp, cands, proc, warpers)
         left_pad, forced_tokens = self._begin_inputs(input_ids, attention_mask, validate, forced_tokens)
         # KV capacity in buckets of 256 positions: evaluation loops with a different prompt length per item reuse one
         # cache, one token buffer ([B, Smax], sliced) and one captured decode graph per bucket
@@ -1751,7 +1774,7 @@ class GARModel:
         out_tokens = self._buf(skey, "out_tokens", (B, Smax), torch.int64, zero=True)[:, :max_new_tokens]
         st["lp"] = self._logprob_planes(skey, out_tokens, (B, Smax)) if return_logprobs else None
         self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
-        eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed)
+        eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed, warpers)
         self._arm_processing(skey, st, proc, eos_list, eos_on_device)
         if _row_words is not None:      # ContinuousBatcher(sampling=True): the rows of this prompt phase pick under requests of their own
             if len(_row_words) != B or sampling is not None:
@@ -1812,9 +1835,10 @@ class GARModel:
         return tuple(self._buf(skey, name, shape, torch.float32, zero=True)[:, :out_tokens.shape[1]]
                      for name in ("lp_raw", "lp_warped"))
 
-    def _arm_state(self, st, left_pad, eos_token_id, sampling, seed):
+    def _arm_state(self, st, left_pad, eos_token_id, sampling, seed, warpers=None):
         """A state's request words before the prompt phase: counters, left_pad, the stopping criterion's latches and eos table, the
-        sampling parameters and Philox key. Returns (eos ids, whether the device holds them)."""
+        sampling parameters and Philox key, and the eight floats of a request with sampling_warpers. Returns (eos ids, whether the
+        device holds them)."""
         st["counters"].zero_()
         if left_pad is None:
             st["left_pad"].zero_()
@@ -1837,12 +1861,16 @@ class GARModel:
                 seed = _draw_seed()
             st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0], torch.float32))
             st["sample_seed"].copy_(self._upload([int(seed)], torch.int64, cache=False))
+        st["warpers"] = sampling is not None and warpers is not None
+        if st["warpers"]:
+            st["sample_ext_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0] + warpers.pack(),
+                                                       torch.float32))
         return eos_list, eos_on_device
 
     def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate, return_logits,
                                sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot,
-                               return_logprobs=False, top_k_lp=0, cands=(), proc=None):
+                               return_logprobs=False, top_k_lp=0, cands=(), proc=None, warpers=None):
         """generate_begin of a num_return_sequences = N > 1 request (do_sample): ONE prompt phase over the B prompts, N first
         tokens drawn from each prompt's logits, and a state of B * N rows for :meth:`generate_finish` — row b * N + i is sample i
         of prompt b, its draws counted by (seed, step, b * N + i) as the replicated batch's would be.
@@ -1870,7 +1898,7 @@ class GARModel:
         st["lp"] = self._logprob_planes(skey, out_tokens, (R, Smax - Sp if shared else Smax)) if return_logprobs else None
         self._topk_planes(skey, st, (R, Smax - Sp if shared else Smax), top_k_lp, list(cands))
         self._arm_state(pst, left_pad, None, None, None)
-        eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed)
+        eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed, warpers)
         self._arm_processing(skey, st, proc, eos_list, eos_on_device)
         to = _PickTargets.of(st, out_tokens)
         first_logits = []
@@ -2113,7 +2141,8 @@ class GARModel:
                 st.get("lp") is not None,                                   # return_logprobs: the step picks with the _lp launch
                 (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0),  # top_logprobs / candidates: one more launch, planes by (k, C)
                 st.get("proc") is not None,                                 # logits_processing: one more launch in front of the pick
-                st.get("row_words") is not None)                            # per-row requests: the step picks with gar_sample_rows
+                st.get("row_words") is not None,                            # per-row requests: the step picks with gar_sample_rows
+                bool(st.get("warpers")))                                    # sampling_warpers: the step draws with gar_sample_ext
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches

@@ -674,6 +674,26 @@ def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed
         check(lib(logits.dtype).gar_sample(*head, stream()), "gar_sample")
 
 
+SAMPLE_EXT_PARAMS = 8                # gar_sample_ext: floats of its parameter block
+
+
+def sample_ext(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed, eos_ids=None, finished=None, done_count=None,
+               row_offset: int = 0, logprobs=None, logprobs_warped=None, n_kept=None):
+    """``gar_sample_ext``: :func:`sample` with ``params`` float32 [8] (device) = temperature, top_p, top_k, 0, min_p, typical_p,
+    epsilon_cutoff, eta_cutoff (``SamplingWarpers.pack()`` behind sample's four) — HF's four further warpers between top-p and the
+    draw. ``logprobs`` / ``logprobs_warped`` as in :func:`sample` (the warped value is under the final kept set); ``n_kept`` int32 [B]
+    (optional): the size of the set each row's token was drawn from. All four off: sample's token and planes bit for bit."""
+    B = logits.shape[0]
+    assert params.dtype == torch.float32 and params.numel() >= SAMPLE_EXT_PARAMS and params.is_contiguous()
+    assert seed.dtype == torch.int64 and seed.numel() >= 1
+    assert n_kept is None or (n_kept.dtype == torch.int32 and n_kept.is_contiguous() and n_kept.numel() >= B)
+    _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped)
+    check(lib(logits.dtype).gar_sample_ext(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
+                                           ptr(step_dev), ptr(cur_tokens), ptr(params), ptr(seed),
+                                           *_latches(B, eos_ids, finished, done_count), int(row_offset), ptr(logprobs),
+                                           ptr(logprobs_warped), ptr(n_kept), stream()), "gar_sample_ext")
+
+
 SAMPLE_ROW_WORDS = 8                 # gar_sample_rows: int32 words of one row's request (continuous.pack_sample_row)
 
 

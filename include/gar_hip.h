@@ -583,6 +583,28 @@ int gar_sample_rows(int dtype, const void* logits, int64_t ld, int B, int V, int
                     const int32_t* step_dev, int64_t* cur_tokens, const int32_t* row_words /* device int32 [B][8] */,
                     const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, gar_stream_t stream);
 
+/* ---- The four further sampling warpers (GARModel.generate(sampling_warpers=SamplingWarpers(...))) ----------------------------------------
+ * Additive: one entry point beside gar_sample / gar_sample_lp / gar_sample_rows, whose signatures and tokens stand, so GAR_ABI_VERSION
+ * stays 16. gar_sample_lp's arguments and results with params_dev float [8] = {temperature, top_p, top_k, 0, min_p, typical_p,
+ * epsilon_cutoff, eta_cutoff}, read on every launch (one captured graph serves any values), both planes nullable (the host launches
+ * the instantiation without the log-probability pass when both are NULL) and one more nullable output, n_kept int32 [B]: the number
+ * of tokens with a finite score in the set row b's token was drawn from. Between top-p and the draw, HF's MinPLogitsWarper ->
+ * TypicalLogitsWarper -> EpsilonLogitsWarper -> EtaLogitsWarper (GenerationMixin._get_logits_processor's order, min_tokens_to_keep
+ * = 1), each over the set the stage before it left, with p its softmax over that set:
+ *   min_p in (0, 1] (0 = off)             remove p < min_p x max p;
+ *   typical_p in (0, 1) (else off)        s = |-log p - H|, H the set's entropy: keep a token iff the tokens of STRICTLY smaller s hold
+ *                                         less than typical_p of the mass (equal s stay or go together; the smallest s always stays);
+ *   epsilon_cutoff in (0, 1) (else off)   remove p < epsilon unless the token's score equals the set's maximum;
+ *   eta_cutoff in (0, 1) (else off)       the same with min(eta, sqrt(eta) x exp(-H)).
+ * lp_warped is the drawn token's log-probability under the final set. With all four off: gar_sample's token and gar_sample_lp's
+ * planes bit for bit (one kernel body forms all of them). One 1024-thread workgroup per row; a stage that is off adds no pass
+ * over the row. Columns V..ld-1 are never read. Reductions of fixed shape: deterministic. No workspace, no allocation, no
+ * synchronisation, hipGraph-capturable. */
+int gar_sample_ext(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
+                   const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev /* device float [8] */,
+                   const int64_t* seed_dev, const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count,
+                   int row_offset, float* lp_raw, float* lp_warped, int32_t* n_kept, gar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
