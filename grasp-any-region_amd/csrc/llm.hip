@@ -4,11 +4,15 @@
 //                  operand with gfx950's transposing LDS read)
 //   embed_lookup   embedding rows of the just-sampled tokens
 //   argmax         greedy sampling with first-index tie break; writes into the device-side token matrix
-//   sample         do_sample = True: temperature / top-k / top-p warpers + one Philox draw per row and step
-//                  (both with an LP instantiation that also writes the chosen token's log-probability;
-//                  one epilogue, commit_token, commits the token; sample_ext: the same body with HF's min_p / typical_p /
-//                  epsilon / eta cutoff warpers between top-p and the draw)
+//   sample         do_sample = True: temperature / top-k / top-p warpers + one Philox draw per row and step — one body (sample_row), one
+//                  radix descent (smp_descent) for its three thresholds, one kernel templated on where a row's request comes from
+//                  (the state's words: gar_sample; those and HF's min_p / typical_p / epsilon / eta cutoff warpers between top-p and
+//                  the draw: gar_sample_ext; a word table per row: gar_sample_rows)
+//                  (argmax and sample both with an LP instantiation that also writes the chosen token's log-probability; one sink,
+//                  PickSink, and one epilogue, commit_token, commit the token)
 //   topk_lp        the k most likely tokens of a step and the log-probabilities of given token ids
+#include <type_traits>
+
 #include "common.h"
 
 // Column of natural dim d0 (first element of an 8-wide slice) inside a q / k head whose rows of W — and therefore whose columns
@@ -202,7 +206,7 @@ extern "C" int gar_embed_lookup(int dtype, const int64_t* tokens, const void* E,
 // ---------------------------------------------------------------------------------------------------------------
 // Token pick. What the greedy kernels, sample_kernel and the topk_lp kernels share is written once here: the order of (value, index)
 // pairs and its wave reduction (beside common.h's wave_sum / wave_max), the two halves of logsumexp over AM_BLOCKS blocks, and the
-// epilogue that commits a row's token. Every reduction has a fixed shape (xor tree inside a wave, waves in order): deterministic.
+// sink a row's token is committed to. Every reduction has a fixed shape (xor tree inside a wave, waves in order): deterministic.
 // ---------------------------------------------------------------------------------------------------------------
 #define AM_BLOCKS 64
 
@@ -238,26 +242,49 @@ __device__ __forceinline__ float merge_exp_sums(float mv, float M, const float* 
     return wave_sum(mv > -INFINITY ? *ps * __expf(mv - M) : 0.f);
 }
 
-// Row b's token of this step: into the token matrix and the current tokens, its log-probabilities into the planes laid out like
-// out_tokens (each may be NULL), and the stopping criterion on the device (HF: EosTokenCriteria over eos_token_id, a list): the
+// Where a pick kernel commits row b's token of a step: the token matrix and the current tokens, the log-probability planes laid out
+// like out_tokens (each may be NULL), and the stopping criterion on the device (HF: EosTokenCriteria over eos_token_id, a list): the
 // FIRST step at which row b produced an end-of-sequence id is latched in finished[b] (-1 = still running), and done_count counts the
 // latched rows — the host's "is every row done" poll reads one int instead of scanning the token matrix (entries < 0 of eos_ids
-// never match).
-__device__ __forceinline__ void commit_token(int b, int tok, int step, int64_t* out_tokens, int64_t out_stride, int64_t* cur_tokens,
-                                             const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count,
-                                             float* lp_raw, float* lp_warped, float raw, float warped) {
-    if (out_tokens) out_tokens[(int64_t)b * out_stride + step] = tok;
-    if (cur_tokens) cur_tokens[b] = tok;
-    if (lp_raw) lp_raw[(int64_t)b * out_stride + step] = raw;
-    if (lp_warped) lp_warped[(int64_t)b * out_stride + step] = warped;
-    if (finished && eos_ids && finished[b] < 0) {
+// never match). Passed by value to the kernels; pick_sink fills and checks it.
+struct PickSink {
+    int64_t* out_tokens;
+    int64_t out_stride;
+    int64_t* cur_tokens;
+    const int64_t* eos_ids;
+    int n_eos;
+    int32_t* finished;
+    int32_t* done_count;
+    float* lp_raw;
+    float* lp_warped;
+};
+
+template <bool LP>          // LP = false: no plane code is compiled
+__device__ __forceinline__ void commit_token(const PickSink& sk, int b, int tok, int col, float raw, float warped) {
+    if (sk.out_tokens) sk.out_tokens[(int64_t)b * sk.out_stride + col] = tok;
+    if (sk.cur_tokens) sk.cur_tokens[b] = tok;
+    if constexpr (LP) {
+        if (sk.lp_raw) sk.lp_raw[(int64_t)b * sk.out_stride + col] = raw;
+        if (sk.lp_warped) sk.lp_warped[(int64_t)b * sk.out_stride + col] = warped;
+    }
+    if (sk.finished && sk.eos_ids && sk.finished[b] < 0) {
         bool hit = false;
-        for (int e = 0; e < n_eos; ++e) hit |= (eos_ids[e] == (int64_t)tok);
+        for (int e = 0; e < sk.n_eos; ++e) hit |= (sk.eos_ids[e] == (int64_t)tok);
         if (hit) {
-            finished[b] = step;
-            if (done_count) atomicAdd(done_count, 1);
+            sk.finished[b] = col;
+            if (sk.done_count) atomicAdd(sk.done_count, 1);
         }
     }
+}
+
+// The sink of an entry point's nine commit arguments. lp: the entry point writes log-probabilities, so it needs a plane.
+static int pick_sink(PickSink& sk, const char* who, bool lp, int64_t* out_tokens, int64_t out_stride, int64_t* cur_tokens,
+                     const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, float* lp_raw, float* lp_warped) {
+    GAR_CHECK_ARG(out_tokens || cur_tokens, "%s: neither out_tokens nor cur_tokens", who);
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "%s: eos_ids / finished", who);
+    GAR_CHECK_ARG(!lp || lp_raw || lp_warped, "%s: no log-probability plane (the entry point without _lp is the form without)", who);
+    sk = {out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, lp_raw, lp_warped};
+    return GAR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -299,6 +326,8 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict
     }
 }
 
+// (the greedy kernels are as they were: this one keeps its scalar parameter list, which compiles to the code it always had, and
+// forms the sink itself)
 template <bool LP>
 __global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
                                                           const float* __restrict__ ps, int64_t* __restrict__ out_tokens,
@@ -317,8 +346,7 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restric
     if (threadIdx.x == 0) {
         const int step = step_dev ? step_dev[0] : 0;
         const float lp = 0.f - logf(s);             // x[tok] - max = 0: HF's processed scores of greedy search are the raw logits
-        commit_token(b, bi, step, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
-                     LP ? lp_raw : nullptr, LP ? lp_warped : nullptr, lp, lp);      // LP = false: no plane code is compiled
+        commit_token<LP>({out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, lp_raw, lp_warped}, b, bi, step, lp, lp);
     }
 }
 
@@ -328,8 +356,9 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restric
 // the reference forwards the caller's GenerationConfig, modeling_gar.py:418-426). One 1024-thread workgroup per row, the row read
 // ~12 times out of L2 (128 k logits: tens of microseconds); no sort:
 //   z = logit / T (fp32 division), ordered by an order-preserving 32-bit key;
-//   top-k: the k-th largest key by a 4 x 8-bit radix descent over COUNTS; keep key >= it (ties at the k-th value stay, as
-//          `scores < topk(scores, k)[0][..., -1]` removes strictly smaller ones only);
+//   top-k: the k-th largest key, that is the smallest key with fewer than k strictly larger ones, by a 4 x 8-bit radix descent
+//          (smp_descent) over COUNTS; keep key >= it (ties at the k-th value stay, as `scores < topk(scores, k)[0][..., -1]` removes
+//          strictly smaller ones only);
 //   top-p: a token stays iff the probability mass of the strictly larger keys is < top_p (HF removes ascending-cumsum <= 1 - top_p:
 //          the same set up to ties, which stay or go together here) — the smallest such key by the same descent over MASS;
 //   draw: u = 24 random bits of Philox4x32-10(key = seed, counter = (step, row)) / 2^24; the token is the first index (in VOCABULARY
@@ -362,8 +391,7 @@ __device__ __forceinline__ unsigned int philox_first(unsigned int c0, unsigned i
 }
 
 // One row's request, as sample_row reads it: the warpers' parameters, the Philox key, the two counter words of the draw (the row's
-// step and its counter row) and the column of the token matrix the token is committed at. gar_sample / gar_sample_lp fill it from the
-// state's words (step = col = step_dev[0], counter row = row_offset + b), gar_sample_rows from row b's eight words.
+// step and its counter row) and the column of the token matrix the token is committed at. sample_kernel fills it from its source.
 struct SmpReq {
     float temperature, top_p;
     int top_k;
@@ -376,8 +404,126 @@ struct SmpReq {
 // The key floor of "keep z >= thr": -0 sorts below +0 in smp_key's order, so a threshold of either zero takes the lower key
 __device__ __forceinline__ unsigned int smp_floor_key(float thr) { return smp_key(thr == 0.f ? -0.f : thr); }
 
-// The body of every sampling kernel: row b's token under rq, drawn by its 1024-thread workgroup (every thread of it calls this, with
-// the same rq) and committed at column rq.col.
+// A sampling workgroup's LDS
+struct SmpLds {
+    float hist_f[SMP_WAVES][256];       // per-wave mass histograms (merged in wave order: deterministic)
+    int hist_i[256];
+    float red_f[SMP_WAVES];
+    float scan_f[SMP_THREADS];
+    unsigned int sh_u[4];
+    float sh_f[4];
+};
+
+// Block reductions of the 1024 threads, every thread gets the result. Fixed shape: xor tree inside a wave, waves in order. The leading
+// barrier frees red_f from the reduction before. The empty asm takes the result where it is written: left alone, the compiler sinks
+// the 16-operand chain to its first use and holds the operands in registers until then (the LP sum across the whole kernel).
+__device__ __forceinline__ float block_sum(SmpLds& L, float v) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) L.red_f[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+    for (int w = 0; w < SMP_WAVES; ++w) t += L.red_f[w];
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
+__device__ __forceinline__ float block_max(SmpLds& L, float v) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) L.red_f[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = L.red_f[0];
+    for (int w = 1; w < SMP_WAVES; ++w) t = fmaxf(t, L.red_f[w]);
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
+// The radix descent of top-k, top-p and typical_p: four levels of 8 bits over 32-bit keys. each(i, key, w) says whether element i is in
+// the set and yields its key and its weight. With the buckets walked from the near end — the largest key (DESC) or the smallest — the
+// result is the LAST key of the set whose strictly nearer keys amount to less than lim, and that amount (`beyond`); the nearest key
+// always qualifies. Acc = int counts elements, in hist_i alone: no float histograms, no float clears, no merge barrier. Acc = float
+// adds the weights, in a fixed order: per-wave histograms, a wave's lanes adding inside one LDS instruction; the waves merged in wave
+// order by threads 0..255; the buckets scanned by thread 0 (hist_i tells an empty bucket from one of mass 0).
+template <typename Acc>
+struct SmpCut {
+    unsigned int key;
+    Acc beyond;
+};
+
+template <typename Acc, bool DESC, typename Each>
+__device__ __forceinline__ SmpCut<Acc> smp_descent(SmpLds& L, int V, Acc lim, Each each) {
+    constexpr bool MASS = std::is_same<Acc, float>::value;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    unsigned int prefix = 0u;
+    Acc beyond = 0;
+#pragma unroll 1                                 // one copy of the body: the levels are separated by barriers anyway
+    for (int level = 3; level >= 0; --level) {
+        const int sh = level * 8;
+        const unsigned int pmask = level == 3 ? 0u : (0xffffffffu << (sh + 8));
+        if constexpr (MASS)
+            for (int i = tid; i < SMP_WAVES * 256; i += SMP_THREADS) (&L.hist_f[0][0])[i] = 0.f;
+        for (int i = tid; i < 256; i += SMP_THREADS) L.hist_i[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < V; i += SMP_THREADS) {     // a wave's 64 consecutive elements per turn
+            unsigned int k;
+            float w;
+            if (each(i, k, w) && (k & pmask) == prefix) {
+                if constexpr (MASS) atomicAdd(&L.hist_f[wave][(k >> sh) & 255u], w);
+                atomicAdd(&L.hist_i[(k >> sh) & 255u], 1);
+            }
+        }
+        __syncthreads();
+        if constexpr (MASS) {
+            if (tid < 256) {
+                float t = 0.f;
+                for (int w = 0; w < SMP_WAVES; ++w) t += L.hist_f[w][tid];
+                L.scan_f[tid] = t;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            // four buckets are read ahead of their turn, so the walk waits for LDS once per four; the amounts are added one by one,
+            // in bucket order, up to the first non-empty bucket that does not qualify
+            int bsel = -1;
+            bool open = true;
+            Acc run = beyond, run_sel = beyond;
+            for (int j0 = 0; j0 < 256 && open; j0 += 4) {
+                int n[4];
+                Acc amount[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = DESC ? 255 - (j0 + u) : j0 + u;
+                    n[u] = L.hist_i[q];
+                    if constexpr (MASS) amount[u] = L.scan_f[q];
+                    else amount[u] = n[u];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (n[u] > 0) {
+                        open = run < lim || bsel < 0;
+                        if (!open) break;
+                        bsel = DESC ? 255 - (j0 + u) : j0 + u;
+                        run_sel = run;
+                    }
+                    run += amount[u];
+                }
+            }
+            L.sh_u[0] = (unsigned int)max(bsel, 0);
+            if constexpr (MASS) L.sh_f[0] = run_sel;
+            else L.sh_u[1] = (unsigned int)run_sel;
+        }
+        __syncthreads();
+        prefix |= L.sh_u[0] << sh;
+        if constexpr (MASS) beyond = L.sh_f[0];
+        else beyond = (Acc)L.sh_u[1];
+        __syncthreads();
+    }
+    return {prefix, beyond};
+}
+
+// The body of the sampling kernel: row b's token under rq, drawn by its 1024-thread workgroup (every thread of it calls this, with
+// the same rq) and committed at column rq.col. Top to bottom: max, top-k, mass, top-p, the EXT stages, draw.
 // LP (gar_sample_lp): the instantiation that also writes the drawn token's log-probabilities — raw = x[tok] - logsumexp(x[0:V]) over the
 // logits as stored, warped = z[tok] - max z - log Z2 over the kept set (the distribution the draw was taken from) — into planes laid
 // out like out_tokens. One more strided pass for sum exp(x - max z * T), reduced by block_sum; LP = false (gar_sample, gar_sample_rows)
@@ -386,218 +532,90 @@ __device__ __forceinline__ unsigned int smp_floor_key(float thr) { return smp_ke
 // over the set the stage before it left (p = e / Z of that set, e = exp(z - mx), mx the ROW maximum: a common shift cancels):
 //   min_p     keep p >= min_p x max p. The row maximum is in the set, so this is e >= min_p: a key floor at mx + log(min_p), no pass;
 //   typical_p s = |(z - mx) - mean|, mean = sum e (z - mx) / Z (the entropy is log Z - mean); keep s <= s_cut, s_cut the largest s whose
-//             strictly smaller s hold less than typical_p of the mass: one pass for (Z, mean), then top-p's four-level descent
-//             run ASCENDING over the bits of s (s >= 0: its bits order like its value). It may remove the maximum;
+//             strictly smaller s hold less than typical_p of the mass: one pass for (Z, mean), then the descent run ASCENDING over
+//             the bits of s (s >= 0: its bits order like its value). It may remove the maximum;
 //   epsilon   keep p >= epsilon, and the set's maximum: one mass pass, a key floor at min(mx + log(epsilon Z), max of the set);
 //   eta       the same with eta' = min(eta, sqrt(eta) exp(-H)), H the set's entropy: one mass + entropy pass.
 // The kept set is ONE predicate, kept(z): the key floor key_lo and, when typical_p acted, s <= typ_cut recomputed from the saved
 // (typ_mean, typ_cut) — every pass after a stage and the draw evaluate exactly it. A stage that is off adds no pass and no barrier;
 // with all four off the instantiation computes gar_sample's token and planes bit for bit. EXT = false compiles none of it.
-template <typename T, bool LP, bool EXT = false>
-__device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int b, const SmpReq& rq,
-                                           int64_t* __restrict__ out_tokens, int64_t out_stride, int64_t* __restrict__ cur_tokens,
-                                           const int64_t* __restrict__ eos_ids, int n_eos, int32_t* __restrict__ finished,
-                                           int32_t* __restrict__ done_count, float* __restrict__ lp_raw,
-                                           float* __restrict__ lp_warped) {
-    __shared__ float hist_f[SMP_WAVES][256];        // per-wave mass histograms (merged in wave order: deterministic)
-    __shared__ int hist_i[256];
-    __shared__ float red_f[SMP_WAVES];
-    __shared__ float scan_f[SMP_THREADS];
-    __shared__ unsigned int sh_u[4];
-    __shared__ float sh_f[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+template <typename T, bool LP, bool EXT>
+__device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int b, const SmpReq& rq, const PickSink& sk) {
+    __shared__ SmpLds L;
+    const int tid = threadIdx.x, lane = tid & 63;
     const float top_p = rq.top_p;
     const int top_k = rq.top_k;
     const float temp = rq.temperature > 0.f ? rq.temperature : 1.0f;       // (the host refuses temperature <= 0, as HF does)
     auto zof = [&](int i) { return DT<T>::ld(row + i) / temp; };
-    auto block_sum = [&](float v) -> float {        // fixed shape: xor tree inside a wave, waves in order
-        v = wave_sum(v);
-        __syncthreads();
-        if (lane == 0) red_f[wave] = v;
-        __syncthreads();
-        float t = 0.f;
-        for (int w = 0; w < SMP_WAVES; ++w) t += red_f[w];
-        return t;
-    };
     // ---- max
     float mx = -INFINITY;
     for (int i = tid; i < V; i += SMP_THREADS) mx = fmaxf(mx, zof(i));
-    mx = wave_max(mx);
-    if (lane == 0) red_f[wave] = mx;
-    __syncthreads();
-    mx = red_f[0];
-    for (int w = 1; w < SMP_WAVES; ++w) mx = fmaxf(mx, red_f[w]);
-    __syncthreads();
+    mx = block_max(L, mx);
     // ---- LP: the mass of the whole row at temperature 1, shifted by xs = max z * T (the row maximum up to one rounding)
     const float xs = mx * temp;
     float Zraw = 0.f;
     if constexpr (LP) {
         float praw = 0.f;
         for (int i = tid; i < V; i += SMP_THREADS) praw += __expf(DT<T>::ld(row + i) - xs);
-        Zraw = block_sum(praw);
+        Zraw = block_sum(L, praw);
     }
-    // ---- top-k: the k-th largest key
-    unsigned int key_lo = 0u;                       // keep key >= key_lo
-    if (top_k > 0 && top_k < V) {
-        unsigned int prefix = 0u;
-        int want = top_k;                           // rank (from the top) still to be found inside the current prefix
-        for (int level = 3; level >= 0; --level) {
-            const int sh = level * 8;
-            const unsigned int pmask = level == 3 ? 0u : (0xffffffffu << (sh + 8));
-            for (int i = tid; i < 256; i += SMP_THREADS) hist_i[i] = 0;
-            __syncthreads();
-            for (int i = tid; i < V; i += SMP_THREADS) {
-                const unsigned int k = smp_key(zof(i));
-                if ((k & pmask) == prefix) atomicAdd(&hist_i[(k >> sh) & 255u], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int bsel = 0, acc = 0;
-                for (int q = 255; q >= 0; --q) {
-                    if (acc + hist_i[q] >= want) { bsel = q; break; }
-                    acc += hist_i[q];
-                }
-                sh_u[0] = (unsigned int)bsel;
-                sh_u[1] = (unsigned int)(want - acc);
-            }
-            __syncthreads();
-            prefix |= sh_u[0] << sh;
-            want = (int)sh_u[1];
-            __syncthreads();
-        }
-        key_lo = prefix;
-    }
-    // ---- mass of what top-k left
-    float part = 0.f;
-    for (int i = tid; i < V; i += SMP_THREADS) {
-        const float z = zof(i);
-        part += smp_key(z) >= key_lo ? __expf(z - mx) : 0.f;
-    }
-    const float Z1 = block_sum(part);
-    // ---- top-p: the smallest key whose strictly-larger keys hold less than top_p of the mass
-    if (top_p < 1.0f) {
-        const float lim = top_p * Z1;
-        unsigned int prefix = 0u;
-        float above = 0.f;
-        for (int level = 3; level >= 0; --level) {
-            const int sh = level * 8;
-            const unsigned int pmask = level == 3 ? 0u : (0xffffffffu << (sh + 8));
-            for (int i = tid; i < SMP_WAVES * 256; i += SMP_THREADS) (&hist_f[0][0])[i] = 0.f;
-            for (int i = tid; i < 256; i += SMP_THREADS) hist_i[i] = 0;
-            __syncthreads();
-            for (int i0 = wave * 64; i0 < V; i0 += SMP_THREADS) {          // a wave's lanes add in lane order inside one DS instruction
-                const int i = i0 + lane;
-                if (i < V) {
-                    const float z = zof(i);
-                    const unsigned int k = smp_key(z);
-                    if (k >= key_lo && (k & pmask) == prefix) {
-                        atomicAdd(&hist_f[wave][(k >> sh) & 255u], __expf(z - mx));
-                        atomicAdd(&hist_i[(k >> sh) & 255u], 1);
-                    }
-                }
-            }
-            __syncthreads();
-            if (tid < 256) {
-                float t = 0.f;
-                for (int w = 0; w < SMP_WAVES; ++w) t += hist_f[w][tid];
-                scan_f[tid] = t;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                // lowest non-empty bucket whose mass-above is still < lim (the top bucket always qualifies: above = 0 at level 3)
-                int bsel = -1;
-                float run = above, run_sel = above;
-                for (int q = 255; q >= 0; --q) {
-                    if (hist_i[q] > 0) {
-                        if (run < lim || bsel < 0) { bsel = q; run_sel = run; }
-                        else break;
-                    }
-                    run += scan_f[q];
-                }
-                sh_u[0] = (unsigned int)max(bsel, 0);
-                sh_f[0] = run_sel;
-            }
-            __syncthreads();
-            prefix |= sh_u[0] << sh;
-            above = sh_f[0];
-            __syncthreads();
-        }
-        key_lo = max(key_lo, prefix);
-    }
-    // ---- EXT: min_p, typical_p, epsilon, eta (see above). typ_on / typ_mean / typ_cut and key_lo are uniform over the workgroup
+    // ---- the kept set: keep key >= key_lo and, EXT, once typical_p acted, s <= typ_cut. All four are uniform over the workgroup
+    unsigned int key_lo = 0u;
     bool typ_on = false;
     float typ_mean = 0.f, typ_cut = 0.f;
     auto kept = [&](float z) -> bool {
         if constexpr (EXT) return smp_key(z) >= key_lo && (!typ_on || fabsf((z - mx) - typ_mean) <= typ_cut);
         else return smp_key(z) >= key_lo;
     };
-    if constexpr (EXT) {
-        auto mass_and_mean = [&](float& Z, float& S) {     // Z = sum e, S = sum e (z - mx) over the kept set (e = 0: no term, never 0 x inf)
-            float pz = 0.f, ps = 0.f;
-            for (int i = tid; i < V; i += SMP_THREADS) {
-                const float z = zof(i);
-                if (kept(z)) {
-                    const float e = __expf(z - mx);
-                    pz += e;
-                    ps += e > 0.f ? e * (z - mx) : 0.f;
-                }
+    // its mass Z = sum e and, with S, S = sum e (z - mx) (e = 0: no term, never 0 x inf)
+    auto kept_mass = [&](float* S) -> float {
+        float pz = 0.f, ps = 0.f;
+        for (int i = tid; i < V; i += SMP_THREADS) {
+            const float z = zof(i);
+            if (kept(z)) {
+                const float e = __expf(z - mx);
+                pz += e;
+                if (S) ps += e > 0.f ? e * (z - mx) : 0.f;
             }
-            Z = block_sum(pz);
-            S = block_sum(ps);
-        };
+        }
+        const float Z = block_sum(L, pz);
+        if (S) *S = block_sum(L, ps);
+        return Z;
+    };
+    // ---- top-k: the k-th largest key
+    if (top_k > 0 && top_k < V)
+        key_lo = smp_descent<int, true>(L, V, top_k, [&](int i, unsigned int& k, float& w) {
+                     k = smp_key(zof(i));
+                     w = 1.f;
+                     return true;
+                 }).key;
+    // ---- mass of what top-k left
+    const float Z1 = kept_mass(nullptr);
+    // ---- top-p: the smallest key whose strictly-larger keys hold less than top_p of the mass
+    if (top_p < 1.0f)
+        key_lo = max(key_lo, smp_descent<float, true>(L, V, top_p * Z1, [&](int i, unsigned int& k, float& w) {
+                                 const float z = zof(i);
+                                 k = smp_key(z);
+                                 w = __expf(z - mx);
+                                 return k >= key_lo;
+                             }).key);
+    // ---- EXT: min_p, typical_p, epsilon, eta (see above)
+    if constexpr (EXT) {
         if (rq.min_p > 0.f) key_lo = max(key_lo, smp_floor_key(mx + logf(rq.min_p)));
         if (rq.typical_p > 0.f && rq.typical_p < 1.0f) {
-            float Zt, St;
-            mass_and_mean(Zt, St);
-            const float mean = St / Zt, lim = rq.typical_p * Zt;
-            unsigned int prefix = 0u;
-            float below = 0.f;
-            for (int level = 3; level >= 0; --level) {
-                const int sh = level * 8;
-                const unsigned int pmask = level == 3 ? 0u : (0xffffffffu << (sh + 8));
-                for (int i = tid; i < SMP_WAVES * 256; i += SMP_THREADS) (&hist_f[0][0])[i] = 0.f;
-                for (int i = tid; i < 256; i += SMP_THREADS) hist_i[i] = 0;
-                __syncthreads();
-                for (int i0 = wave * 64; i0 < V; i0 += SMP_THREADS) {
-                    const int i = i0 + lane;
-                    if (i < V) {
-                        const float z = zof(i);
-                        const unsigned int k = __float_as_uint(fabsf((z - mx) - mean));
-                        if (kept(z) && (k & pmask) == prefix) {         // (typ_on is still false: the set min_p left)
-                            atomicAdd(&hist_f[wave][(k >> sh) & 255u], __expf(z - mx));
-                            atomicAdd(&hist_i[(k >> sh) & 255u], 1);
-                        }
-                    }
-                }
-                __syncthreads();
-                if (tid < 256) {
-                    float t = 0.f;
-                    for (int w = 0; w < SMP_WAVES; ++w) t += hist_f[w][tid];
-                    scan_f[tid] = t;
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    // highest non-empty bucket whose mass-below is still < lim (the lowest one always qualifies: HF keeps one token)
-                    int bsel = -1;
-                    float run = below, run_sel = below;
-                    for (int q = 0; q < 256; ++q) {
-                        if (hist_i[q] > 0) {
-                            if (run < lim || bsel < 0) { bsel = q; run_sel = run; }
-                            else break;
-                        }
-                        run += scan_f[q];
-                    }
-                    sh_u[0] = (unsigned int)max(bsel, 0);
-                    sh_f[0] = run_sel;
-                }
-                __syncthreads();
-                prefix |= sh_u[0] << sh;
-                below = sh_f[0];
-                __syncthreads();
-            }
+            float St;
+            const float Zt = kept_mass(&St);
+            const float mean = St / Zt;
+            // the largest s whose strictly smaller s hold less than typical_p of the mass (the smallest always qualifies: HF keeps one token)
+            const SmpCut<float> cut = smp_descent<float, false>(L, V, rq.typical_p * Zt, [&](int i, unsigned int& k, float& w) {
+                const float z = zof(i);
+                k = __float_as_uint(fabsf((z - mx) - mean));
+                w = __expf(z - mx);
+                return kept(z);                     // (typ_on is still false: the set min_p left)
+            });
             typ_on = true;
             typ_mean = mean;
-            typ_cut = __uint_as_float(prefix);
+            typ_cut = __uint_as_float(cut.key);
         }
         const bool eps_on = rq.epsilon > 0.f && rq.epsilon < 1.0f, eta_on = rq.eta > 0.f && rq.eta < 1.0f;
         float m2 = mx;                              // the maximum of the set: the row's unless typical_p removed it
@@ -607,31 +625,21 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
                 const float z = zof(i);
                 if (kept(z)) m2 = fmaxf(m2, z);
             }
-            m2 = wave_max(m2);
-            __syncthreads();
-            if (lane == 0) red_f[wave] = m2;
-            __syncthreads();
-            m2 = red_f[0];
-            for (int w = 1; w < SMP_WAVES; ++w) m2 = fmaxf(m2, red_f[w]);
+            m2 = block_max(L, m2);
         }
         if (eps_on) {
-            float pz = 0.f;
-            for (int i = tid; i < V; i += SMP_THREADS) {
-                const float z = zof(i);
-                pz += kept(z) ? __expf(z - mx) : 0.f;
-            }
-            const float Ze = block_sum(pz);
+            const float Ze = kept_mass(nullptr);
             key_lo = max(key_lo, smp_floor_key(fminf(mx + logf(rq.epsilon * Ze), m2)));
         }
         if (eta_on) {
-            float Zh, Sh;
-            mass_and_mean(Zh, Sh);
+            float Sh;
+            const float Zh = kept_mass(&Sh);
             const float H = logf(Zh) - Sh / Zh;
             const float cut = fminf(rq.eta, sqrtf(rq.eta) * __expf(-H));
             key_lo = max(key_lo, smp_floor_key(fminf(mx + logf(cut * Zh), m2)));
         }
         if (rq.n_kept) {
-            if (tid == 0) hist_i[0] = 0;
+            if (tid == 0) L.hist_i[0] = 0;
             __syncthreads();
         }
     }
@@ -646,24 +654,24 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
         csum += k ? __expf(z - mx) : 0.f;
         if constexpr (EXT) ckept += (k && z > -INFINITY) ? 1 : 0;
     }
-    scan_f[tid] = csum;
+    L.scan_f[tid] = csum;
     if constexpr (EXT) {
         if (rq.n_kept) {                            // integer adds: any order gives the same count
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) ckept += __shfl_xor(ckept, o, 64);
-            if (lane == 0 && ckept) atomicAdd(&hist_i[0], ckept);
+            if (lane == 0 && ckept) atomicAdd(&L.hist_i[0], ckept);
         }
     }
     __syncthreads();
     if (tid < SMP_WAVES) {                          // 16 segment sums of 64 chunks each, sequential: a fixed order
         float t = 0.f;
-        for (int j = 0; j < 64; ++j) t += scan_f[tid * 64 + j];
-        red_f[tid] = t;
+        for (int j = 0; j < 64; ++j) t += L.scan_f[tid * 64 + j];
+        L.red_f[tid] = t;
     }
     __syncthreads();
     if (tid == 0) {
         float Z2 = 0.f;
-        for (int w = 0; w < SMP_WAVES; ++w) Z2 += red_f[w];
+        for (int w = 0; w < SMP_WAVES; ++w) Z2 += L.red_f[w];
         const unsigned int r = philox_first(rq.step, rq.crow, 0u, 0u, rq.seed_lo, rq.seed_hi);
         const float u = (float)(r >> 8) * (1.0f / 16777216.0f);
         const float target = u * Z2;
@@ -671,18 +679,18 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
         float run = 0.f;
         int seg = SMP_WAVES - 1;
         for (int w = 0; w < SMP_WAVES; ++w) {
-            if (run + red_f[w] > target) { seg = w; break; }
-            run += red_f[w];
+            if (run + L.red_f[w] > target) { seg = w; break; }
+            run += L.red_f[w];
         }
-        if (seg == SMP_WAVES - 1 && !(run + red_f[seg] > target)) {       // rounding at the very end: fall back to the whole last segment
+        if (seg == SMP_WAVES - 1 && !(run + L.red_f[seg] > target)) {     // rounding at the very end: fall back to the whole last segment
             run = 0.f;
-            for (int w = 0; w < seg; ++w) run += red_f[w];
+            for (int w = 0; w < seg; ++w) run += L.red_f[w];
         }
         int ch = seg * 64 + 63, lastnz = -1;
         float run_nz = run;
         bool found = false;
         for (int j = 0; j < 64; ++j) {
-            const float cs = scan_f[seg * 64 + j];
+            const float cs = L.scan_f[seg * 64 + j];
             if (run + cs > target) { ch = seg * 64 + j; found = true; break; }
             if (cs > 0.f) { lastnz = seg * 64 + j; run_nz = run; }
             run += cs;
@@ -692,21 +700,21 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
             run = run_nz;
             found = true;
         }
-        sh_u[0] = (unsigned int)ch;
-        sh_u[1] = found ? 1u : 0u;
-        sh_f[0] = run;
-        sh_f[1] = target;
-        if constexpr (LP) sh_f[2] = Z2;
+        L.sh_u[0] = (unsigned int)ch;
+        L.sh_u[1] = found ? 1u : 0u;
+        L.sh_f[0] = run;
+        L.sh_f[1] = target;
+        if constexpr (LP) L.sh_f[2] = Z2;
         if constexpr (EXT) {
-            if (rq.n_kept) rq.n_kept[b] = hist_i[0];
+            if (rq.n_kept) rq.n_kept[b] = L.hist_i[0];
         }
     }
     __syncthreads();
-    if (tid == (int)sh_u[0] || (!sh_u[1] && tid == 0)) {
+    if (tid == (int)L.sh_u[0] || (!L.sh_u[1] && tid == 0)) {
         int tok = -1;
-        if (sh_u[1] && tid == (int)sh_u[0]) {
-            float run = sh_f[0];
-            const float target = sh_f[1];
+        if (L.sh_u[1] && tid == (int)L.sh_u[0]) {
+            float run = L.sh_f[0];
+            const float target = L.sh_f[1];
             for (int i = c0; i < c1; ++i) {
                 const float z = zof(i);
                 if (kept(z)) {
@@ -724,85 +732,86 @@ __device__ __forceinline__ void sample_row(const T* __restrict__ row, int V, int
             float raw = 0.f, warped = 0.f;
             if constexpr (LP) {
                 raw = (DT<T>::ld(row + tok) - xs) - logf(Zraw);
-                warped = (zof(tok) - mx) - logf(sh_f[2]);
+                warped = (zof(tok) - mx) - logf(L.sh_f[2]);
             }
-            commit_token(b, tok, rq.col, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
-                         LP ? lp_raw : nullptr, LP ? lp_warped : nullptr, raw, warped);
+            commit_token<LP>(sk, b, tok, rq.col, raw, warped);
         }
     }
 }
 
-// gar_sample / gar_sample_lp: one request for all rows, out of the state's words
-template <typename T, bool LP>
-__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V,
-                                                             int64_t* __restrict__ out_tokens, int64_t out_stride,
-                                                             const int32_t* __restrict__ step_dev, int64_t* __restrict__ cur_tokens,
-                                                             const float* __restrict__ params, const int64_t* __restrict__ seed_dev,
-                                                             const int64_t* __restrict__ eos_ids, int n_eos,
-                                                             int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
-                                                             int row_offset, float* __restrict__ lp_raw,
-                                                             float* __restrict__ lp_warped) {
-    const int b = blockIdx.x;
-    const int step = step_dev ? step_dev[0] : 0;
-    const unsigned long long seed = (unsigned long long)seed_dev[0];
-    const SmpReq rq = {params[0], params[1], (int)params[2], (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)step,
-                       (unsigned int)(b + row_offset), step};
-    sample_row<T, LP>(logits + (int64_t)b * ld, V, b, rq, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count,
-                      lp_raw, lp_warped);
-}
+// The sampling kernel, one workgroup per row, templated on where row b's request comes from:
+//   SMP_STATE      gar_sample / gar_sample_lp: one request for all rows out of the state's words — params [3] = {temperature, top_p,
+//                  top_k}, seed_dev [1]; step = col = step_dev[0], counter row = row_offset + b;
+//   SMP_STATE_EXT  gar_sample_ext: the same with params [8] = {temperature, top_p, top_k, 0, min_p, typical_p, epsilon_cutoff,
+//                  eta_cutoff} and the nullable n_kept [B]: sample_row's EXT instantiation;
+//   SMP_ROWS       gar_sample_rows: every row its own request, out of row_words [B][8] = {mode, temperature bits, top_p bits, top_k,
+//                  seed low, seed high, col0, counter row}. The column is the shared step_dev[0]; the row's step is its distance from
+//                  col0. Mode 0 picks the largest logit as stored in am_better's order (gar_argmax's token) with the row's own
+//                  workgroup and draws nothing. The branch on the mode is uniform over the workgroup (one word per row), so the
+//                  barriers of either side are reached by all of its threads or by none.
+enum { SMP_STATE, SMP_STATE_EXT, SMP_ROWS };
 
-// gar_sample_rows: every row its own request, out of row_words [B][8] = {mode, temperature bits, top_p bits, top_k, seed low, seed
-// high, col0, counter row}. The column is the shared step_dev[0]; the row's step is its distance from col0. Mode 0 picks the largest
-// logit as stored in am_better's order (gar_argmax's token) with the row's own workgroup and draws nothing. The branch on the mode is
-// uniform over the workgroup (one word per row), so the barriers of either side are reached by all of its threads or by none.
-template <typename T>
-__global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(const T* __restrict__ logits, int64_t ld, int V,
-                                                                  int64_t* __restrict__ out_tokens, int64_t out_stride,
-                                                                  const int32_t* __restrict__ step_dev,
-                                                                  int64_t* __restrict__ cur_tokens,
-                                                                  const int32_t* __restrict__ row_words,
-                                                                  const int64_t* __restrict__ eos_ids, int n_eos,
-                                                                  int32_t* __restrict__ finished, int32_t* __restrict__ done_count) {
-    __shared__ float gv[SMP_WAVES];
-    __shared__ int gi[SMP_WAVES];
+struct SmpSource {
+    const int32_t* step_dev;            // NULL: column 0
+    const float* params;                // SMP_STATE, SMP_STATE_EXT
+    const int64_t* seed_dev;
+    int row_offset;
+    int32_t* n_kept;                    // SMP_STATE_EXT
+    const int32_t* row_words;           // SMP_ROWS
+};
+
+template <typename T, bool LP, int SRC>
+__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V, SmpSource src,
+                                                             PickSink sk) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const T* row = logits + (int64_t)b * ld;
-    const int32_t* w = row_words + (int64_t)b * 8;
-    const int col = step_dev ? step_dev[0] : 0;
-    if (w[0] == 0) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int i = tid; i < V; i += SMP_THREADS) am_better(bv, bi, DT<T>::ld(row + i), i);
-        wave_best(bv, bi);
-        if ((tid & 63) == 0) { gv[tid >> 6] = bv; gi[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int k = 1; k < SMP_WAVES; ++k) am_better(bv, bi, gv[k], gi[k]);
-            commit_token(b, bi, col, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr, 0.f,
-                         0.f);
+    const int col = src.step_dev ? src.step_dev[0] : 0;
+    SmpReq rq;
+    if constexpr (SRC == SMP_ROWS) {
+        __shared__ float gv[SMP_WAVES];
+        __shared__ int gi[SMP_WAVES];
+        const int32_t* w = src.row_words + (int64_t)b * 8;
+        if (w[0] == 0) {
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            for (int i = tid; i < V; i += SMP_THREADS) am_better(bv, bi, DT<T>::ld(row + i), i);
+            wave_best(bv, bi);
+            if ((tid & 63) == 0) { gv[tid >> 6] = bv; gi[tid >> 6] = bi; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int k = 1; k < SMP_WAVES; ++k) am_better(bv, bi, gv[k], gi[k]);
+                commit_token<false>(sk, b, bi, col, 0.f, 0.f);
+            }
+            return;
         }
-        return;
+        rq = {__int_as_float(w[1]), __int_as_float(w[2]), w[3], (unsigned int)w[4], (unsigned int)w[5],
+              (unsigned int)max(0, col - w[6]), (unsigned int)w[7], col};
+    } else {
+        const unsigned long long seed = (unsigned long long)src.seed_dev[0];
+        rq = {src.params[0], src.params[1], (int)src.params[2], (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)col,
+              (unsigned int)(b + src.row_offset), col};
+        if constexpr (SRC == SMP_STATE_EXT) {
+            rq.min_p = src.params[4];
+            rq.typical_p = src.params[5];
+            rq.epsilon = src.params[6];
+            rq.eta = src.params[7];
+            rq.n_kept = src.n_kept;
+        }
     }
-    const SmpReq rq = {__int_as_float(w[1]), __int_as_float(w[2]), w[3], (unsigned int)w[4], (unsigned int)w[5],
-                       (unsigned int)max(0, col - w[6]), (unsigned int)w[7], col};
-    sample_row<T, false>(row, V, b, rq, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr);
+    sample_row<T, LP, SRC == SMP_STATE_EXT>(row, V, b, rq, sk);
 }
 
-template <bool LP>
-static int sample_launch(const char* who, int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
-                         int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev,
-                         const int64_t* seed_dev, const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count,
-                         int row_offset, float* lp_raw, float* lp_warped, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0, "%s: bad args", who);
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "%s: eos_ids / finished", who);
-    if (LP) GAR_CHECK_ARG(lp_raw || lp_warped, "%s: no log-probability plane (gar_sample is the form without)", who);
+template <bool LP, int SRC>
+static int sample_launch(const char* who, int dtype, const void* logits, int64_t ld, int B, int V, const SmpSource& src,
+                         const PickSink& sk, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && B > 0 && V > 0 && (SRC == SMP_ROWS ? src.row_words != nullptr
+                                                               : src.params && src.seed_dev && src.row_offset >= 0),
+                  "%s: bad args", who);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((sample_kernel<bf16_t, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+        hipLaunchKernelGGL((sample_kernel<bf16_t, LP, SRC>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, src, sk);
     else
-        hipLaunchKernelGGL((sample_kernel<float, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens, out_stride,
-                           step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped);
+        hipLaunchKernelGGL((sample_kernel<float, LP, SRC>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, src, sk);
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }
@@ -811,94 +820,52 @@ extern "C" int gar_sample(int dtype, const void* logits, int64_t ld, int B, int 
                           const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
                           const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
                           gar_stream_t stream) {
-    return sample_launch<false>("sample", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev,
-                                eos_ids, n_eos, finished, done_count, row_offset, nullptr, nullptr, stream);
+    PickSink sk;
+    if (int e = pick_sink(sk, "sample", false, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr))
+        return e;
+    return sample_launch<false, SMP_STATE>("sample", dtype, logits, ld, B, V, {step_dev, params_dev, seed_dev, row_offset, nullptr, nullptr},
+                                           sk, stream);
 }
 
 extern "C" int gar_sample_lp(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
                              const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
                              float* lp_raw, float* lp_warped, gar_stream_t stream) {
-    return sample_launch<true>("sample_lp", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev,
-                               eos_ids, n_eos, finished, done_count, row_offset, lp_raw, lp_warped, stream);
+    PickSink sk;
+    if (int e = pick_sink(sk, "sample_lp", true, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, lp_raw, lp_warped))
+        return e;
+    return sample_launch<true, SMP_STATE>("sample_lp", dtype, logits, ld, B, V, {step_dev, params_dev, seed_dev, row_offset, nullptr, nullptr},
+                                          sk, stream);
 }
 
-// gar_sample_ext: gar_sample / gar_sample_lp with params [8] = {temperature, top_p, top_k, 0, min_p, typical_p, epsilon_cutoff,
-// eta_cutoff} and the nullable n_kept [B]; the host picks LP by the planes
-template <typename T, bool LP>
-__global__ __launch_bounds__(SMP_THREADS) void sample_ext_kernel(const T* __restrict__ logits, int64_t ld, int V,
-                                                                 int64_t* __restrict__ out_tokens, int64_t out_stride,
-                                                                 const int32_t* __restrict__ step_dev, int64_t* __restrict__ cur_tokens,
-                                                                 const float* __restrict__ params, const int64_t* __restrict__ seed_dev,
-                                                                 const int64_t* __restrict__ eos_ids, int n_eos,
-                                                                 int32_t* __restrict__ finished, int32_t* __restrict__ done_count,
-                                                                 int row_offset, float* __restrict__ lp_raw,
-                                                                 float* __restrict__ lp_warped, int32_t* __restrict__ n_kept) {
-    const int b = blockIdx.x;
-    const int step = step_dev ? step_dev[0] : 0;
-    const unsigned long long seed = (unsigned long long)seed_dev[0];
-    const SmpReq rq = {params[0], params[1], (int)params[2], (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)step,
-                       (unsigned int)(b + row_offset), step, params[4], params[5], params[6], params[7], n_kept};
-    sample_row<T, LP, true>(logits + (int64_t)b * ld, V, b, rq, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished,
-                            done_count, lp_raw, lp_warped);
-}
-
-template <bool LP>
-static void sample_ext_launch(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
-                              const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
-                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset, float* lp_raw,
-                              float* lp_warped, int32_t* n_kept, hipStream_t s) {
-    if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((sample_ext_kernel<bf16_t, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens,
-                           out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset,
-                           lp_raw, lp_warped, n_kept);
-    else
-        hipLaunchKernelGGL((sample_ext_kernel<float, LP>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens,
-                           out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids, n_eos, finished, done_count, row_offset,
-                           lp_raw, lp_warped, n_kept);
-}
-
+// the host picks LP by the planes
 extern "C" int gar_sample_ext(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
                               const int32_t* step_dev, int64_t* cur_tokens, const float* params_dev, const int64_t* seed_dev,
                               const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, int row_offset,
                               float* lp_raw, float* lp_warped, int32_t* n_kept, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && params_dev && seed_dev && B > 0 && V > 0 && (out_tokens || cur_tokens) && row_offset >= 0,
-                  "sample_ext: bad args");
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample_ext: eos_ids / finished");
-    if (lp_raw || lp_warped)
-        sample_ext_launch<true>(dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids,
-                                n_eos, finished, done_count, row_offset, lp_raw, lp_warped, n_kept, (hipStream_t)stream);
-    else
-        sample_ext_launch<false>(dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, params_dev, seed_dev, eos_ids,
-                                 n_eos, finished, done_count, row_offset, nullptr, nullptr, n_kept, (hipStream_t)stream);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+    PickSink sk;
+    if (int e = pick_sink(sk, "sample_ext", false, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, lp_raw, lp_warped))
+        return e;
+    const SmpSource src = {step_dev, params_dev, seed_dev, row_offset, n_kept, nullptr};
+    return lp_raw || lp_warped ? sample_launch<true, SMP_STATE_EXT>("sample_ext", dtype, logits, ld, B, V, src, sk, stream)
+                               : sample_launch<false, SMP_STATE_EXT>("sample_ext", dtype, logits, ld, B, V, src, sk, stream);
 }
 
 extern "C" int gar_sample_rows(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens, int64_t out_stride,
                                const int32_t* step_dev, int64_t* cur_tokens, const int32_t* row_words, const int64_t* eos_ids,
                                int n_eos, int32_t* finished, int32_t* done_count, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && row_words && B > 0 && V > 0 && (out_tokens || cur_tokens), "sample_rows: bad args");
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "sample_rows: eos_ids / finished");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == GAR_BF16)
-        hipLaunchKernelGGL((sample_rows_kernel<bf16_t>), dim3(B), dim3(SMP_THREADS), 0, s, (const bf16_t*)logits, ld, V, out_tokens,
-                           out_stride, step_dev, cur_tokens, row_words, eos_ids, n_eos, finished, done_count);
-    else
-        hipLaunchKernelGGL((sample_rows_kernel<float>), dim3(B), dim3(SMP_THREADS), 0, s, (const float*)logits, ld, V, out_tokens,
-                           out_stride, step_dev, cur_tokens, row_words, eos_ids, n_eos, finished, done_count);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+    PickSink sk;
+    if (int e = pick_sink(sk, "sample_rows", false, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr))
+        return e;
+    return sample_launch<false, SMP_ROWS>("sample_rows", dtype, logits, ld, B, V, {step_dev, nullptr, nullptr, 0, nullptr, row_words}, sk,
+                                          stream);
 }
 
 // workspace: pv | pi (gar_argmax), pv | pi | ps (gar_argmax_lp), AM_BLOCKS entries per row each
 template <bool LP>
-static int argmax_launch(const char* who, int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
-                         int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace, const int64_t* eos_ids,
-                         int n_eos, int32_t* finished, int32_t* done_count, float* lp_raw, float* lp_warped, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0 && (out_tokens || cur_tokens), "%s: bad args", who);
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && (!finished || eos_ids), "%s: eos_ids / finished", who);
-    if (LP) GAR_CHECK_ARG(lp_raw || lp_warped, "%s: no log-probability plane (gar_argmax is the form without)", who);
+static int argmax_launch(const char* who, int dtype, const void* logits, int64_t ld, int B, int V, const int32_t* step_dev,
+                         void* workspace, const PickSink& sk, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && workspace && B > 0 && V > 0, "%s: bad args", who);
     float* pv = (float*)workspace;
     int* pi = (int*)(pv + (int64_t)B * AM_BLOCKS);
     float* ps = LP ? pv + (int64_t)B * AM_BLOCKS * 2 : nullptr;
@@ -908,8 +875,8 @@ static int argmax_launch(const char* who, int dtype, const void* logits, int64_t
         hipLaunchKernelGGL((argmax_partial_kernel<bf16_t, LP>), grid, dim3(256), 0, s, (const bf16_t*)logits, ld, V, pv, pi, ps);
     else
         hipLaunchKernelGGL((argmax_partial_kernel<float, LP>), grid, dim3(256), 0, s, (const float*)logits, ld, V, pv, pi, ps);
-    hipLaunchKernelGGL(argmax_final_kernel<LP>, dim3(B), dim3(64), 0, s, pv, pi, ps, out_tokens, out_stride, step_dev, cur_tokens,
-                       eos_ids, n_eos, finished, done_count, lp_raw, lp_warped);
+    hipLaunchKernelGGL(argmax_final_kernel<LP>, dim3(B), dim3(64), 0, s, pv, pi, ps, sk.out_tokens, sk.out_stride, step_dev, sk.cur_tokens,
+                       sk.eos_ids, sk.n_eos, sk.finished, sk.done_count, sk.lp_raw, sk.lp_warped);
     GAR_CHECK_LAUNCH();
     return GAR_OK;
 }
@@ -922,8 +889,10 @@ extern "C" int64_t gar_argmax_workspace(int B, int V) {
 extern "C" int gar_argmax(int dtype, const void* logits, int64_t ld, int B, int V, int64_t* out_tokens,
                           int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace,
                           const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, gar_stream_t stream) {
-    return argmax_launch<false>("argmax", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids,
-                                n_eos, finished, done_count, nullptr, nullptr, stream);
+    PickSink sk;
+    if (int e = pick_sink(sk, "argmax", false, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, nullptr, nullptr))
+        return e;
+    return argmax_launch<false>("argmax", dtype, logits, ld, B, V, step_dev, workspace, sk, stream);
 }
 
 extern "C" int64_t gar_argmax_lp_workspace(int B, int V) {
@@ -935,8 +904,10 @@ extern "C" int gar_argmax_lp(int dtype, const void* logits, int64_t ld, int B, i
                              int64_t out_stride, const int32_t* step_dev, int64_t* cur_tokens, void* workspace,
                              const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count, float* lp_raw,
                              float* lp_warped, gar_stream_t stream) {
-    return argmax_launch<true>("argmax_lp", dtype, logits, ld, B, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids,
-                               n_eos, finished, done_count, lp_raw, lp_warped, stream);
+    PickSink sk;
+    if (int e = pick_sink(sk, "argmax_lp", true, out_tokens, out_stride, cur_tokens, eos_ids, n_eos, finished, done_count, lp_raw, lp_warped))
+        return e;
+    return argmax_launch<true>("argmax_lp", dtype, logits, ld, B, V, step_dev, workspace, sk, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

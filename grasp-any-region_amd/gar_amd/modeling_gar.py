@@ -1200,11 +1200,10 @@ class GARModel:
             eos_ids=self._buf(key, "eos_ids", (self.MAX_EOS_IDS,), torch.int64),
             finished=self._buf(key, "finished", (B,), torch.int32),
             done_count=self._buf(key, "done_count", (1,), torch.int32, zero=True),
-            # do_sample = True (gar_sample): [temperature, top_p, top_k] and the Philox key of the request, read by the captured step
-            sample_params=self._buf(key, "sample_params", (4,), torch.float32, zero=True),
+            # do_sample = True: the request's sampling block and Philox key, read by the captured step — [temperature, top_p, top_k, 0]
+            # (gar_sample reads the first three), then sampling_warpers' [min_p, typical_p, epsilon_cutoff, eta_cutoff] (gar_sample_ext)
+            sample_params=self._buf(key, "sample_params", (ops.SAMPLE_EXT_PARAMS,), torch.float32, zero=True),
             sample_seed=self._buf(key, "sample_seed", (1,), torch.int64, zero=True),
-            # sampling_warpers (gar_sample_ext): sample_params' four floats, then [min_p, typical_p, epsilon_cutoff, eta_cutoff]
-            sample_ext_params=self._buf(key, "sample_ext_params", (ops.SAMPLE_EXT_PARAMS,), torch.float32, zero=True),
             sampling=False,
             slot=slot,
         )
@@ -1434,7 +1433,7 @@ class GARModel:
             ops.sample_rows(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, to.row_words, eos_ids=st["eos_ids"],
                             finished=to.finished, done_count=st["done_count"])
         elif st.get("sampling") and st.get("warpers"):          # sampling_warpers: the same pick through gar_sample_ext
-            ops.sample_ext(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_ext_params"], st["sample_seed"],
+            ops.sample_ext(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_params"], st["sample_seed"],
                            row_offset=to.row0, **latches)
         elif st.get("sampling"):
             ops.sample(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, st["sample_params"], st["sample_seed"],
@@ -1859,12 +1858,10 @@ class GARModel:
         if sampling is not None:
             if seed is None:
                 seed = _draw_seed()
-            st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0], torch.float32))
+            tail = warpers.pack() if warpers is not None else [0.0, 1.0, 0.0, 0.0]         # no sampling_warpers: all four off
+            st["sample_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0] + tail, torch.float32))
             st["sample_seed"].copy_(self._upload([int(seed)], torch.int64, cache=False))
         st["warpers"] = sampling is not None and warpers is not None
-        if st["warpers"]:
-            st["sample_ext_params"].copy_(self._upload([sampling[0], sampling[1], float(sampling[2]), 0.0] + warpers.pack(),
-                                                       torch.float32))
         return eos_list, eos_on_device
 
     def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,

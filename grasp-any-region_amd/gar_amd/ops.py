@@ -630,12 +630,16 @@ def _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
     return logprobs is not None or logprobs_warped is not None
 
 
-def _latches(B, eos_ids, finished, done_count):
-    """the stopping criterion's four arguments of :func:`argmax` / :func:`sample`: eos table, its length, the two latches"""
+def _pick_args(logits, V, out_tokens, out_stride, step_dev, cur_tokens, source, eos_ids, finished, done_count):
+    """what the pick entry points (:func:`argmax`, :func:`sample`, :func:`sample_ext`, :func:`sample_rows`) share of their argument
+    lists: the logits and the token placement, then ``source`` — the pointers each has of its own there (workspace / params and
+    seed / row words) — then the stopping criterion's four: eos table, its length, the two latches"""
+    B = logits.shape[0]
     assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
     assert finished is None or (eos_ids is not None and finished.dtype == torch.int32 and finished.is_contiguous()
                                 and finished.numel() == B)
-    return ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count)
+    return (dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride, ptr(step_dev), ptr(cur_tokens),
+            *(ptr(t) for t in source), ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), ptr(finished), ptr(done_count))
 
 
 def argmax(logits, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, eos_ids=None, finished=None, done_count=None,
@@ -645,11 +649,9 @@ def argmax(logits, V, out_tokens, out_stride, step_dev, cur_tokens, workspace, e
     criterion evaluated on the device (all optional). ``logprobs`` / ``logprobs_warped``: f32 planes shaped and strided like
     ``out_tokens``; with either one the launch is ``gar_argmax_lp`` (``workspace`` >= :func:`argmax_lp_workspace` bytes), which
     also writes the chosen token's log-probability at the step's column — equal in both planes for greedy search."""
-    B = logits.shape[0]
-    head = (dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride, ptr(step_dev),
-            ptr(cur_tokens), ptr(workspace), *_latches(B, eos_ids, finished, done_count))
+    head = _pick_args(logits, V, out_tokens, out_stride, step_dev, cur_tokens, (workspace,), eos_ids, finished, done_count)
     if _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
-        assert workspace.numel() * workspace.element_size() >= argmax_lp_workspace(B, V)
+        assert workspace.numel() * workspace.element_size() >= argmax_lp_workspace(logits.shape[0], V)
         check(lib(logits.dtype).gar_argmax_lp(*head, ptr(logprobs), ptr(logprobs_warped), stream()), "gar_argmax_lp")
     else:
         check(lib(logits.dtype).gar_argmax(*head, stream()), "gar_argmax")
@@ -663,11 +665,10 @@ def sample(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, seed
     prompt chunks draws what the un-chunked batch draws (ABI 15). ``logprobs`` / ``logprobs_warped``: f32 planes shaped and strided
     like ``out_tokens``; with either one the launch is ``gar_sample_lp``, which also writes the drawn token's log-probability under
     the raw logits / under the warped distribution it was drawn from."""
-    B = logits.shape[0]
     assert params.dtype == torch.float32 and params.numel() >= 3 and params.is_contiguous()
     assert seed.dtype == torch.int64 and seed.numel() >= 1
-    head = (dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride, ptr(step_dev),
-            ptr(cur_tokens), ptr(params), ptr(seed), *_latches(B, eos_ids, finished, done_count), int(row_offset))
+    head = (*_pick_args(logits, V, out_tokens, out_stride, step_dev, cur_tokens, (params, seed), eos_ids, finished, done_count),
+            int(row_offset))
     if _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped):
         check(lib(logits.dtype).gar_sample_lp(*head, ptr(logprobs), ptr(logprobs_warped), stream()), "gar_sample_lp")
     else:
@@ -688,10 +689,9 @@ def sample_ext(logits, V, out_tokens, out_stride, step_dev, cur_tokens, params, 
     assert seed.dtype == torch.int64 and seed.numel() >= 1
     assert n_kept is None or (n_kept.dtype == torch.int32 and n_kept.is_contiguous() and n_kept.numel() >= B)
     _lp_planes(out_tokens, out_stride, logprobs, logprobs_warped)
-    check(lib(logits.dtype).gar_sample_ext(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
-                                           ptr(step_dev), ptr(cur_tokens), ptr(params), ptr(seed),
-                                           *_latches(B, eos_ids, finished, done_count), int(row_offset), ptr(logprobs),
-                                           ptr(logprobs_warped), ptr(n_kept), stream()), "gar_sample_ext")
+    head = _pick_args(logits, V, out_tokens, out_stride, step_dev, cur_tokens, (params, seed), eos_ids, finished, done_count)
+    check(lib(logits.dtype).gar_sample_ext(*head, int(row_offset), ptr(logprobs), ptr(logprobs_warped), ptr(n_kept), stream()),
+          "gar_sample_ext")
 
 
 SAMPLE_ROW_WORDS = 8                 # gar_sample_rows: int32 words of one row's request (continuous.pack_sample_row)
@@ -706,9 +706,8 @@ def sample_rows(logits, V, out_tokens, out_stride, step_dev, cur_tokens, row_wor
     B = logits.shape[0]
     assert logits.dim() == 2 and logits.stride(1) == 1
     assert row_words.dtype == torch.int32 and row_words.is_contiguous() and tuple(row_words.shape) == (B, SAMPLE_ROW_WORDS)
-    check(lib(logits.dtype).gar_sample_rows(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), out_stride,
-                                            ptr(step_dev), ptr(cur_tokens), ptr(row_words),
-                                            *_latches(B, eos_ids, finished, done_count), stream()), "gar_sample_rows")
+    head = _pick_args(logits, V, out_tokens, out_stride, step_dev, cur_tokens, (row_words,), eos_ids, finished, done_count)
+    check(lib(logits.dtype).gar_sample_rows(*head, stream()), "gar_sample_rows")
 
 
 def argmax_workspace(B, V) -> int:
