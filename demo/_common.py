@@ -34,6 +34,14 @@ def base_parser(description):
                          "(16-bit models, decode batches <= 64 rows; the prompt phase keeps 16-bit weights)")
     ap.add_argument("--num_return_sequences", type=int, default=1,
                     help="N > 1: N sampled captions of the region from ONE prompt phase (implies sampling; --seed keys the draws)")
+    ap.add_argument("--num_beams", type=int, default=1, metavar="K",
+                    help="K > 1: beam search with K beams over one prompt phase; --num_return_sequences N <= K then prints the N "
+                         "best hypotheses with their scores (not combined with the sampling flags)")
+    ap.add_argument("--length_penalty", type=float, default=1.0,
+                    help="beam search: a hypothesis of n tokens scores sum of log-probabilities / n ** length_penalty")
+    ap.add_argument("--early_stopping", choices=("false", "true", "never"), default="false",
+                    help="beam search: HF's early_stopping (false: its default heuristic, true: stop at K hypotheses, never: "
+                         "the canonical criterion)")
     ap.add_argument("--temperature", type=float, default=None, help="sampling temperature (implies sampling)")
     ap.add_argument("--top_p", type=float, default=None, help="nucleus sampling (implies sampling)")
     ap.add_argument("--top_k", type=int, default=None, help="top-k sampling (implies sampling)")
@@ -81,6 +89,8 @@ def generation_config(args, processor):
               pad_token_id=processor.tokenizer.pad_token_id)
     knobs = {k: getattr(args, k, None) for k in ("temperature", "top_p", "top_k")}
     n = getattr(args, "num_return_sequences", 1)
+    if getattr(args, "num_beams", 1) > 1:       # beam search: --num_return_sequences goes to beam_search_kwargs
+        n = 1
     # the reference CLI is greedy: sampling only when asked for
     if n != 1 or any(v is not None for v in knobs.values()) or any(v is not None for v in _warper_args(args).values()):
         gc.update(do_sample=True, num_return_sequences=n, **{k: v for k, v in knobs.items() if v is not None})
@@ -102,6 +112,24 @@ def sampling_kwargs(args, gc):
     from gar_amd import SamplingWarpers
     sw = SamplingWarpers(**_warper_args(args))
     return dict(seed=args.seed) if sw.neutral else dict(seed=args.seed, sampling_warpers=sw)
+
+
+def beam_search_kwargs(args):
+    """generate() keywords of --num_beams / --length_penalty / --early_stopping: the beam_search parameter when K > 1"""
+    if getattr(args, "num_beams", 1) <= 1:
+        return {}
+    from gar_amd import BeamSearch
+    return dict(beam_search=BeamSearch(args.num_beams, length_penalty=args.length_penalty,
+                                       early_stopping={"false": False, "true": True, "never": "never"}[args.early_stopping],
+                                       num_return_sequences=getattr(args, "num_return_sequences", 1)))
+
+
+def print_hypotheses(out, tokenizer):
+    """beam search: one line per returned hypothesis, best first; with several, each behind its score"""
+    many = len(out.sequences) > 1
+    for seq, score in zip(out.sequences, out.sequences_scores.tolist()):
+        text = tokenizer.decode(seq, skip_special_tokens=True).strip()
+        print(f"[{score:.4f}] {text}" if many else text)
 
 
 def logits_processing_kwargs(args):

@@ -4,7 +4,8 @@
 import numpy as np
 from PIL import Image
 
-from _common import base_parser, generation_config, load, logits_processing_kwargs, sampling_kwargs, top_logprob_lines
+from _common import (base_parser, beam_search_kwargs, generation_config, load, logits_processing_kwargs, print_hypotheses,
+                     sampling_kwargs, top_logprob_lines)
 
 
 def main():
@@ -26,7 +27,10 @@ def main():
     data_sample = dataset[0]
     gc = generation_config(args, processor)
     out = model.generate(**data_sample, generation_config=gc, return_dict=True, top_logprobs=args.top_logprobs,
-                         **sampling_kwargs(args, gc), **logits_processing_kwargs(args))
+                         **sampling_kwargs(args, gc), **logits_processing_kwargs(args), **beam_search_kwargs(args))
+    if out.sequences_scores is not None:    # --num_beams: the hypotheses, best first
+        print_hypotheses(out, processor.tokenizer)
+        return
     for r, seq in enumerate(out.sequences):     # one answer, or the --num_return_sequences sampled ones
         print(processor.tokenizer.decode(seq, skip_special_tokens=True).strip())
         if args.top_logprobs:

@@ -4,7 +4,8 @@ demo/gar_with_mask.py (same flags: --model_name_or_path --image_path --mask_path
 import numpy as np
 from PIL import Image
 
-from _common import base_parser, generation_config, load, logits_processing_kwargs, sampling_kwargs, top_logprob_lines
+from _common import (base_parser, beam_search_kwargs, generation_config, load, logits_processing_kwargs, print_hypotheses,
+                     sampling_kwargs, top_logprob_lines)
 
 
 def main():
@@ -26,7 +27,11 @@ def main():
     data_sample = dataset[0]
     gc = generation_config(args, processor)
     out = model.generate(**data_sample, generation_config=gc, return_dict=True, return_logprobs=args.return_logprobs,
-                         top_logprobs=args.top_logprobs, **sampling_kwargs(args, gc), **logits_processing_kwargs(args))
+                         top_logprobs=args.top_logprobs, **sampling_kwargs(args, gc), **logits_processing_kwargs(args),
+                         **beam_search_kwargs(args))
+    if out.sequences_scores is not None:    # --num_beams: the hypotheses, best first
+        print_hypotheses(out, processor.tokenizer)
+        return
     if args.return_logprobs:                # the model's own confidence in each caption: mean log-probability of its tokens
         mean = (out.sum_logprobs / out.n_tokens.clamp(min=1)).tolist()
         for r in sorted(range(len(mean)), key=lambda i: -mean[i]):

@@ -5,7 +5,8 @@ computation goes through the C-ABI HIP library ``libgar_hip.so`` (include/gar_hi
 PyTorch fallback: importing :mod:`gar_amd.hip` without the built library raises.
 """
 from .configuration_gar import GARConfig, PerceptionLMConfig, TextConfig, VisionConfig  # noqa: F401
+from .beam_search import BeamSearch  # noqa: F401
 from .logits_processing import LogitsProcessing  # noqa: F401
 from .sampling_warpers import SamplingWarpers  # noqa: F401
 
-__all__ = ["GARConfig", "PerceptionLMConfig", "TextConfig", "VisionConfig", "LogitsProcessing", "SamplingWarpers"]
+__all__ = ["GARConfig", "PerceptionLMConfig", "TextConfig", "VisionConfig", "LogitsProcessing", "SamplingWarpers", "BeamSearch"]

@@ -165,7 +165,7 @@ class ContinuousBatcher:
 
     # ---- queue ------------------------------------------------------------------------------------------------------
     def submit(self, sample: dict, generation_config=None, seed: Optional[int] = None, sampling_warpers=None,
-               **generate_kwargs) -> int:
+               beam_search=None, **generate_kwargs) -> int:
         """queue one region. The generation options are read as ``generate`` reads them (a GenerationConfig / dict with the
         keyword arguments laid over it; HF's defaults, so ``top_k`` 50): ``do_sample=True`` — on a batcher built with
         ``sampling=True`` — makes this ticket a sampled one under its own temperature / top_k / top_p and ``seed`` (None: drawn
@@ -181,6 +181,8 @@ class ContinuousBatcher:
             raise hip.GarError("ContinuousBatcher.submit: sampling_warpers is not implemented (call generate(sampling_warpers=...))")
         if sample.get("return_logprobs"):
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
+        if beam_search is not None or sample.get("beam_search") is not None:
+            raise hip.GarError("ContinuousBatcher.submit: beam_search is not implemented (call generate(beam_search=...))")
         request = self._read_options(generation_config, generate_kwargs, seed)
         t = self._next_ticket
         self._next_ticket += 1

@@ -40,6 +40,13 @@ class GemmParams(C.Structure):
                 ("qkv_pos_dev", C.c_void_p), ("qkv_left_pad", C.c_void_p), ("norm_folded", C.c_int32)]
 
 
+class BeamState(C.Structure):
+    """gar_beam_state (include/gar_hip.h): the buffers of a beam-search request and the shape words of its launch"""
+    _fields_ = [(n, C.c_void_p) for n in ("top_ids", "top_lp", "run_scores", "cur_tokens", "parent", "hist", "fin_tokens",
+                                          "fin_scores", "fin_len", "fin_flag", "heur", "done", "done_count", "params", "len_pow",
+                                          "step_dev")] + [(n, C.c_int32) for n in ("B", "K", "M", "T", "V")]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SIGNATURES = {
     "gar_abi_version": ([], _i),
@@ -106,6 +113,8 @@ SIGNATURES = {
     "gar_lm_head_xent_takes": ([_i, _i, _i, _i], _i),
     "gar_lm_head_xent_strips": ([_i], _i),
     "gar_lm_head_xent": ([_i, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "gar_beam_step": ([C.POINTER(BeamState), _vp], _i),
+    "gar_kv_beam_reorder": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "gar_xent_combine": ([_i, _vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
 }
 

@@ -21,6 +21,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 import torch
 
 from . import hip, ops
+from .beam_search import BeamBudgetError, BeamSearch
 from .configuration_gar import GARConfig
 from .logits_processing import LogitsProcessing, _Refused as _ProcessingRefused
 from .sampling_warpers import SamplingWarpers
@@ -65,6 +66,9 @@ class GenerateOutput:
     #                                                         by ascending id — entry 0 is the greedy token
     top_logprobs: Optional[torch.Tensor] = None             # f32 [B * N, n, k]: their log-probabilities
     candidate_logprobs: Optional[torch.Tensor] = None       # f32 [B * N, n, C]: log-probabilities of candidate_token_ids, in their order
+    # beam_search=BeamSearch(...) only: ``sequences`` is [B * num_return_sequences, n], each prompt's hypotheses best
+    # first, ``pad`` behind each one's end; this is each one's sum of log-probabilities / length ** length_penalty
+    sequences_scores: Optional[torch.Tensor] = None         # f32 [B * num_return_sequences]
 
 
 class _PickTargets(NamedTuple):
@@ -266,13 +270,18 @@ _LOGITS_PROCESSING_FIELDS = ("repetition_penalty", "no_repeat_ngram_size", "min_
                              "begin_suppress_tokens", "bad_words_ids")
 
 
+# the refused options that generate(beam_search=...) provides under a parameter of its own
+_BEAM_SEARCH_FIELDS = ("num_beams", "length_penalty")
+
+
 def _refuse_non_greedy(get):
     for name, neutral in _NEUTRAL_GENERATION_OPTIONS.items():
         v = get(name)
         if name == "num_return_sequences" and get("do_sample", False):
             continue                                        # sampling: read by _num_return_sequences
         if not any((v is n) or (n is not None and not isinstance(v, bool) and v == n) for n in neutral):
-            hint = " — pass generate(logits_processing=LogitsProcessing(...)) instead" if name in _LOGITS_PROCESSING_FIELDS else ""
+            hint = " — pass generate(logits_processing=LogitsProcessing(...)) instead" if name in _LOGITS_PROCESSING_FIELDS else \
+                (" — pass generate(beam_search=BeamSearch(...)) instead" if name in _BEAM_SEARCH_FIELDS else "")
             raise hip.GarError(f"generation option {name}={v!r} is not implemented (greedy search only: it would change the tokens "
                                f"and is refused rather than ignored){hint}")
 
@@ -462,6 +471,8 @@ class GenerationPipeline:
     PRIORITY = 0        # of the decode stream (-1 = high)
 
     def __init__(self, model: "GARModel", **generate_kwargs):
+        if generate_kwargs.get("beam_search") is not None:
+            raise hip.GarError("GenerationPipeline / generate_pipelined: beam_search is not implemented (call generate)")
         self.model, self.kwargs = model, generate_kwargs
         self.side = None
         self.done = {}              # slot -> event: that slot's previous decode loop has finished
@@ -491,6 +502,8 @@ class GenerationPipeline:
         if early:
             outs.append(self._finish(self.prev))
             self.prev = None
+        if sample.get("beam_search") is not None:
+            raise hip.GarError("GenerationPipeline / generate_pipelined: beam_search is not implemented (call generate)")
         slot = self.n & 1
         self.n += 1
         with torch.cuda.device(m.device):
@@ -1420,6 +1433,9 @@ class GARModel:
         gar_sample_rows instead."""
         B, tk, step = logits.shape[0], to.tk, st["counters"][2:3]
         key = ("head", B, st.get("slot", 0))
+        if st.get("beam") is not None:      # beam_search: the rows' M best, the beams' bookkeeping, the caches behind their parents
+            self._beam_pick(logits, V, st, key)
+            return
         if process:
             self._process(logits, V, st, to.out_tokens)
         if tk is not None:
@@ -1442,6 +1458,105 @@ class GARModel:
             name, size = ("amws", ops.argmax_workspace) if to.lp is None else ("amws_lp", ops.argmax_lp_workspace)
             ws = self._buf(key, name, (size(B, V),), torch.uint8)
             ops.argmax(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, ws, **latches)
+
+    def _beam_pick(self, logits, V, st, key):
+        """a decode step's pick of a beam_search request: gar_topk_lp (k = M) into the beam state's planes, gar_beam_step, then
+        gar_kv_beam_reorder over the cache rows the beams have written so far — counters[2] of them, from suffix row 0 of the
+        shared layout or from the prompt length (counters[3]) of the f32 parity mode's ordinary cache"""
+        bs, step = st["beam"], st["counters"][2:3]
+        R, M = bs["B"] * bs["K"], bs["M"]
+        ws = self._buf(key, f"tkws{M}", (ops.topk_lp_workspace(R, V, M),), torch.uint8)
+        ops.topk_lp(logits, V, None, ws, top_ids=bs["top_ids"].view(R, 1, M), top_lp=bs["top_lp"].view(R, 1, M))
+        ops.beam_step(bs, step, V)
+        ops.kv_beam_reorder(st["Kc"], st["Vc"], bs["K"], step, bs["parent"], s0_dev=None if st.get("fan") else st["counters"][3:4])
+
+    _BEAM_LATCHES = ("run_scores", "parent", "hist", "fin_tokens", "fin_scores", "fin_len", "fin_flag", "heur", "done")
+
+    def _beam_state(self, skey, st, B: int, K: int, M: int, T: int, beam: BeamSearch, max_new_tokens: int, eos_list):
+        """st["beam"] of a request: the buffers gar_beam_step reads and writes — buffers of the state named by (K, M, T), so their
+        pointers are the captured step's — initialised as HF initialises them, with the request's parameter block and
+        length-penalty table uploaded"""
+        R = B * K
+
+        def buf(name, shape, dt):
+            return self._buf(skey, f"beam_{name}_{K}_{M}_{T}", shape, dt, zero=True)
+        bs = dict(B=B, K=K, M=M, T=T, key=(K, M, T), cur_tokens=st["cur"], done_count=st["done_count"],
+                  top_ids=buf("top_ids", (R, M), torch.int32), top_lp=buf("top_lp", (R, M), torch.float32),
+                  run_scores=buf("run_scores", (R,), torch.float32), parent=buf("parent", (R,), torch.int32),
+                  hist=buf("hist", (2, R, T), torch.int32), fin_tokens=buf("fin_tokens", (R, T), torch.int32),
+                  fin_scores=buf("fin_scores", (R,), torch.float32), fin_len=buf("fin_len", (R,), torch.int32),
+                  fin_flag=buf("fin_flag", (R,), torch.int32), heur=buf("heur", (B,), torch.int32),
+                  done=buf("done", (B,), torch.int32), params=buf("params", (ops.BEAM_PARAM_WORDS,), torch.int32),
+                  len_pow=buf("len_pow", (T,), torch.float32))
+        for name in ("parent", "hist", "fin_tokens", "fin_len", "fin_flag", "done"):
+            bs[name].zero_()
+        bs["run_scores"].fill_(-1.0e9)              # HF: the first beam starts at 0, its siblings at -1e9, the finished set at -1e9
+        bs["run_scores"].view(B, K)[:, 0].zero_()
+        bs["fin_scores"].fill_(-1.0e9)
+        bs["heur"].fill_(1)
+        bs["params"].copy_(self._upload(beam.pack(max_new_tokens, eos_list), torch.int32))
+        bs["len_pow"].copy_(self._upload(beam.length_powers(T), torch.float32))
+        st["beam"] = bs
+        return bs
+
+    def _generate_begin_beam(self, beam, M, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
+                             max_new_tokens, eos_token_id, pad_token_id, use_graph, validate, return_logits, sync_every,
+                             feature_replay_video, video_frame_tokens, state_slot):
+        """generate_begin of a beam_search request, :meth:`_generate_begin_fanout` with N = K: ONE prompt phase over the B prompts
+        and a state of B * K rows — row b * K + j is beam j of prompt b. The prompt's logits row is repeated K times and step 0 is
+        an ordinary gar_beam_step: HF's initial scores {0, -1e9, ...} make every first candidate a child of beam 0.
+        16-bit models: the beams share the prompt's cache rows and keep only their generated tokens' rows. f32 parity mode: the
+        prompt's rows are copied into an ordinary (B * K, Smax) state."""
+        t = self.config.mllm_config.text_config
+        B, S = input_ids.shape
+        K = beam.num_beams
+        R, V = B * K, t.vocab_size
+        left_pad, _ = self._begin_inputs(input_ids, attention_mask, validate, None)
+        shared = self.dtype in HALF_DTYPES
+        T = _round_up(max_new_tokens, 64)
+        if shared:
+            Sp = _round_up(S, 256)
+            _, pst = self._llm_state(B, Sp, state_slot)
+            skey, st = self._llm_state(R, T, state_slot, fan=(B, Sp))
+            st["fan"] = dict(B=B, N=K, Sp=Sp, Kp=pst["Kc"], Vp=pst["Vc"], left_pad=pst["left_pad"])
+            Smax = Sp + T
+        else:
+            Sp = Smax = _round_up(S + max_new_tokens, 256)
+            _, pst = self._llm_state(B, Smax, state_slot)
+            skey, st = self._llm_state(R, Smax, state_slot)
+        out_tokens = self._buf(skey, "out_tokens", (R, T if shared else Smax), torch.int64, zero=True)[:, :max_new_tokens]
+        st["lp"] = st["tk"] = st["proc"] = None
+        self._arm_state(pst, left_pad, None, None, None)
+        eos_list, _ = self._arm_state(st, None, eos_token_id, None, None)
+        bs = self._beam_state(skey, st, B, K, M, T, beam, max_new_tokens, eos_list)
+        first_logits = []
+        for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
+                                                  feature_replay_video, video_frame_tokens):
+            last = self._prefill(embeds, pst, Sp, b0)
+            lg = self._head(last, b1 - b0, pst, None).repeat_interleave(K, 0)       # the SAME logits for the K beams
+            r0, r1 = _fanout_rows(b0, b1, K)
+            ws = self._buf(("head", r1 - r0, state_slot), f"tkws{M}", (ops.topk_lp_workspace(r1 - r0, V, M),), torch.uint8)
+            ops.topk_lp(lg, V, None, ws, top_ids=bs["top_ids"][r0:r1].view(r1 - r0, 1, M), top_lp=bs["top_lp"][r0:r1].view(r1 - r0, 1, M))
+            if return_logits:
+                first_logits.append(lg[:, :V].float())
+        c = st["counters"]
+        ops.beam_step(bs, c[2:3], V)            # step 0 of every prompt (counters are zero): nothing to reorder yet
+        if shared:                      # [t, -, step, P]
+            c[2:3].fill_(1)
+            c[3:4].fill_(S)
+        else:                           # the prompts' cache rows, K times; [pos, kv_len, step, prompt length]
+            L, Hkv, hd = t.num_hidden_layers, t.num_key_value_heads, t.head_dim
+            for name in ("Kc", "Vc"):
+                st[name].view(L, B, K, Hkv, Smax, hd).copy_(pst[name][:, :, None])
+            st["left_pad"].copy_(pst["left_pad"].repeat_interleave(K))
+            c[0:1].fill_(S)
+            c[1:2].fill_(S + 1)
+            c[2:3].fill_(1)
+            c[3:4].fill_(S)
+        return self._begin_pending(first_logits, eos_list, eos_on_device=True, st=st, skey=skey, B=R, Smax=Smax,
+                                   out_tokens=out_tokens, max_new_tokens=max_new_tokens, pad_token_id=pad_token_id,
+                                   return_logits=return_logits, forced_tokens=None, use_graph=use_graph, validate=validate,
+                                   sync_every=sync_every, N=K, beam=beam, prompts=B)
 
     def _topk_planes(self, skey, st, shape, k: int, cands):
         """st["tk"] of a request: None without top_logprobs / candidate_token_ids, else the planes gar_topk_lp writes — buffers of the
@@ -1683,7 +1798,7 @@ class GARModel:
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
                        top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None, logits_processing=None,
-                       sampling_warpers=None, _row_words=None, **generate_kwargs) -> "_PendingGeneration":
+                       sampling_warpers=None, beam_search=None, _row_words=None, **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
         the request; None draws one from torch's global generator).
@@ -1722,7 +1837,28 @@ class GARModel:
         the draw, each over the tokens the stage before it left. Needs ``do_sample=True`` (``ValueError`` otherwise).
         ``token_logprobs_warped`` is then the drawn token's log-probability under the final kept set. None or all-neutral values:
         the path, the launches and the captured graph of a call without it. The GenerationConfig fields of the same names stay
-        refused."""
+        refused.
+
+        ``beam_search``: a :class:`BeamSearch` (or a dict of its fields) — HF's beam search (``GenerationMixin._beam_search``,
+        do_sample=False) on the device: ``num_beams`` beams per prompt over ONE prompt phase and, in the 16-bit
+        modes, one shared prompt cache. ``sequences`` is then [B * num_return_sequences, n] — each prompt's hypotheses best first,
+        ``pad`` behind each one's end, n the longest returned one — and ``sequences_scores`` holds their scores. Equal scores
+        order by (beam, token) ascending where HF leaves them to torch.topk. Refused with ``GarError``: together with
+        ``do_sample``, ``sampling_warpers``, ``logits_processing`` (HF processes the log-probabilities behind the softmax with each
+        beam's own history: a follow-up), ``return_logprobs`` / ``top_logprobs`` / ``candidate_token_ids``, ``forced_tokens`` and
+        ``kv_cache_dtype="fp8"``, and ``num_beams * max(2, 1 + number of eos ids) > 32``. The GenerationConfig fields
+        ``num_beams`` / ``length_penalty`` stay refused."""
+        beam = BeamSearch.coerce(beam_search)
+        if beam is not None:
+            for name, on in (("sampling_warpers", sampling_warpers is not None), ("logits_processing", logits_processing is not None),
+                             ("return_logprobs", return_logprobs), ("top_logprobs", top_logprobs),
+                             ("candidate_token_ids", candidate_token_ids), ("forced_tokens", forced_tokens is not None),
+                             ("per-row requests", _row_words is not None)):
+                if on:
+                    raise hip.GarError(f"beam_search with {name} is not implemented (DESIGN 7.11)")
+            if self.kv_cache_dtype == "fp8":
+                raise hip.GarError("beam_search with kv_cache_dtype='fp8' is not implemented (the beams' cache rows are reordered as "
+                                   "16-bit / f32 rows, and the shared-prefix decode attention reads 16-bit caches)")
         warpers = SamplingWarpers.coerce(sampling_warpers)
         warpers = None if warpers.neutral else warpers
         proc = LogitsProcessing.coerce(logits_processing)
@@ -1741,6 +1877,8 @@ class GARModel:
         N = 1
         get = _option_reader(generation_config, generate_kwargs)
         if get is not None:
+            if beam is not None and get("do_sample", False):
+                raise hip.GarError("beam_search with do_sample=True (beam-search multinomial sampling) is not implemented")
             N = _num_return_sequences(get, self.kv_cache_dtype)
             _refuse_non_greedy(get)
             if get("do_sample", False):
@@ -1759,6 +1897,19 @@ class GARModel:
         max_new_tokens = int(max_new_tokens or 64)
         cfg = self.config
         B, S = input_ids.shape
+        if beam is not None:
+            n_eos = 0 if eos_token_id is None else (len(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else 1)
+            try:            # HF's beams_to_keep: known only now that the eos ids are
+                M = beam.candidates(n_eos)
+                beam.pack(max_new_tokens, [0] * n_eos)
+            except BeamBudgetError as e:
+                raise hip.GarError(str(e)) from None
+            if M > cfg.mllm_config.text_config.vocab_size:
+                raise hip.GarError(f"beam_search: {M} candidates per step above vocab_size {cfg.mllm_config.text_config.vocab_size}")
+            self._check_decode_rows(B * beam.num_beams, "generate(beam_search=...)")
+            return self._generate_begin_beam(beam, M, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids,
+                                             attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, validate,
+                                             return_logits, sync_every, feature_replay_video, video_frame_tokens, state_slot)
         self._check_decode_rows(B * N, "generate")
         if N > 1:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
@@ -2054,6 +2205,7 @@ class GARModel:
         max_new_tokens, eos, eos_first, pad_token_id = pend.max_new_tokens, pend.eos, pend.eos_first, pend.pad_token_id
         return_logits, all_logits, forced_tokens = pend.return_logits, pend.all_logits, pend.forced_tokens
         use_graph, validate, sync_every = pend.use_graph, pend.validate, pend.sync_every
+        beam = getattr(pend, "beam", None)
         self._input_flags = pend.input_flags
         # tensors the prompt phase allocated (possibly on another stream: GenerationPipeline) and this loop reads: the caching
         # allocator must not hand their memory to that stream's next allocation before this stream is done with them
@@ -2079,7 +2231,15 @@ class GARModel:
             n_done += 1
             if forced_tokens is not None and n_done - 1 < forced_tokens.shape[1]:
                 st["cur"].copy_(forced_tokens[:, n_done - 1])
-            if eos and (n_done % sync_every == 0 or n_done == max_new_tokens):
+            if beam is not None:
+                # every prompt done? gar_beam_step latches each prompt's and counts them; without eos ids none is before the last step
+                if eos and (n_done % sync_every == 0 or n_done == max_new_tokens):
+                    fin = int(st["done_count"].item()) >= pend.prompts
+                    if not validate:
+                        self._raise_on_input_flags()
+                    if fin:
+                        break
+            elif eos and (n_done % sync_every == 0 or n_done == max_new_tokens):
                 # every row done? ONE int off the device (the argmax kernel latches each row's first eos step and counts the
                 # latched rows); a list longer than MAX_EOS_IDS keeps the host scan of the token matrix
                 fin = int(st["done_count"].item()) >= B if pend.eos_on_device else \
@@ -2089,6 +2249,8 @@ class GARModel:
                 if fin:
                     break
         ops.KERNEL_PHASE = ""
+        if beam is not None:
+            return self._beam_output(pend, torch.stack(all_logits, 1) if return_logits else None)
         seq = out_tokens[:, :n_done].clone()
         if eos:
             if pend.eos_on_device:      # finished[b] = the column of row b's first eos (-1: none within n_done tokens)
@@ -2113,6 +2275,19 @@ class GARModel:
             lp_fields.update(top_logprob_outputs(st["tk"], seq.shape[1], finished_at if eos else [None] * B))
         return GenerateOutput(sequences=seq, logits=torch.stack(all_logits, 1) if return_logits else None,
                               input_flags=None if validate else self._input_flags, **lp_fields)
+
+    def _beam_output(self, pend, logits) -> GenerateOutput:
+        """the output of a beam_search request from the finished set the steps kept: the best num_return_sequences hypotheses of
+        every prompt, cropped to the longest and padded behind each one's end (HF: ``pad_token_id``, else the first eos id)"""
+        bs, beam, B = pend.st["beam"], pend.beam, pend.prompts
+        K, T, n = bs["K"], bs["T"], beam.num_return_sequences
+        lens = bs["fin_len"].view(B, K)[:, :n].reshape(-1).to(torch.int64)
+        width = int(lens.max().item())
+        seq = bs["fin_tokens"].view(B, K, T)[:, :n, :width].reshape(B * n, width).to(torch.int64)
+        pad = pend.pad_token_id if pend.pad_token_id is not None else (pend.eos_first or 0)
+        seq = torch.where(torch.arange(width, device=self.device)[None, :] < lens[:, None], seq, torch.full_like(seq, int(pad)))
+        return GenerateOutput(sequences=seq, logits=logits, input_flags=None if pend.validate else self._input_flags,
+                              sequences_scores=bs["fin_scores"].view(B, K)[:, :n].reshape(-1).clone())
 
     def _raise_on_input_flags(self):
         f = int(self._input_flags.item())
@@ -2139,16 +2314,22 @@ class GARModel:
                 (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0),  # top_logprobs / candidates: one more launch, planes by (k, C)
                 st.get("proc") is not None,                                 # logits_processing: one more launch in front of the pick
                 st.get("row_words") is not None,                            # per-row requests: the step picks with gar_sample_rows
-                bool(st.get("warpers")))                                    # sampling_warpers: the step draws with gar_sample_ext
+                bool(st.get("warpers")),                                    # sampling_warpers: the step draws with gar_sample_ext
+                st["beam"]["key"] if st.get("beam") else None)              # beam_search: the step picks with gar_beam_step, buffers by (K, M, T)
         g = self._graphs.get(gkey)
         if g is None:
             # what the warm-up step writes and the loop reads: counters, the current tokens, the stopping-criterion latches
             names = ("counters", "cur", "finished", "done_count")
             saved = {n: st[n].clone() for n in names}
+            # beam_search: the warm-up step also moves the beams' scores, histories, finished set and latches. The cache rows it
+            # reorders are the ones it has just appended, which the first real step writes again
+            beam_saved = {n: st["beam"][n].clone() for n in self._BEAM_LATCHES} if st.get("beam") else {}
 
             def restore():
                 for n in names:
                     st[n].copy_(saved[n])
+                for n, v in beam_saved.items():
+                    st["beam"][n].copy_(v)
             s = torch.cuda.Stream(device=self.device)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):                       # warm-up launch outside capture (lazy module load)

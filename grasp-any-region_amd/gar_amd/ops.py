@@ -840,3 +840,42 @@ def xent_combine(targets, dest, S: int, token_logprobs, sum_logprobs, n_tokens, 
                                    0 if logits is None else logits.stride(0), R, int(V), ptr(targets), ptr(dest), int(S),
                                    ptr(token_logprobs), ptr(sum_logprobs), ptr(n_tokens), ptr(flags), stream()),
           "gar_xent_combine")
+
+
+# ---- beam search (GARModel.generate(beam_search=...); include/gar_hip.h, gar_beam_step / gar_kv_beam_reorder) ----------------
+BEAM_PARAM_WORDS = 20                # GAR_BEAM_PARAM_WORDS: int32 words of gar_beam_step's parameter block
+
+
+def beam_step(bs: dict, step_dev, V: int):
+    """``gar_beam_step`` on the beam state ``bs``: B, K, M, T and the tensors ``top_ids`` int32 / ``top_lp`` f32 [B * K, M] (what
+    gar_topk_lp wrote for this step), ``run_scores`` f32 / ``cur_tokens`` int64 / ``parent`` int32 [B * K], ``hist`` int32
+    [2, B * K, T], ``fin_tokens`` int32 [B * K, T], ``fin_scores`` f32 / ``fin_len`` / ``fin_flag`` int32 [B * K], ``heur`` /
+    ``done`` int32 [B], ``done_count`` int32 [1], ``params`` int32 [BEAM_PARAM_WORDS], ``len_pow`` f32 [T]. One step of HF's beam
+    search for every prompt whose done latch is clear, at step ``step_dev[0]`` (None = 0)."""
+    B, K, M, T = bs["B"], bs["K"], bs["M"], bs["T"]
+    R = B * K
+    shapes = dict(top_ids=((R, M), torch.int32), top_lp=((R, M), torch.float32), run_scores=((R,), torch.float32),
+                  cur_tokens=((R,), torch.int64), parent=((R,), torch.int32), hist=((2, R, T), torch.int32),
+                  fin_tokens=((R, T), torch.int32), fin_scores=((R,), torch.float32), fin_len=((R,), torch.int32),
+                  fin_flag=((R,), torch.int32), heur=((B,), torch.int32), done=((B,), torch.int32), done_count=((1,), torch.int32),
+                  params=((BEAM_PARAM_WORDS,), torch.int32), len_pow=((T,), torch.float32))
+    st = hip.BeamState()
+    for name, (shape, dt) in shapes.items():
+        t = bs[name]
+        assert tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous() and t.is_cuda, (name, tuple(t.shape), shape, t.dtype)
+        setattr(st, name, ptr(t))
+    st.step_dev = ptr(step_dev) or None
+    st.B, st.K, st.M, st.T, st.V = B, K, M, T, int(V)
+    check(lib().gar_beam_step(st, stream()), "gar_beam_step")
+
+
+def kv_beam_reorder(Kc, Vc, K: int, n_dev, parent, s0: int = 0, s0_dev=None):
+    """``gar_kv_beam_reorder``: in the caches ``Kc`` / ``Vc`` [L, R, Hkv, cap, hd] (2- or 4-byte elements, contiguous), row
+    b * K + j takes the bytes of row b * K + parent[b * K + j] over positions s0 .. s0 + n_dev[0] - 1 (``s0_dev`` int32 [1]
+    replaces ``s0`` when given), in place, one launch for all layers and both caches."""
+    assert Kc.shape == Vc.shape and Kc.dtype == Vc.dtype and Kc.dim() == 5 and Kc.is_contiguous() and Vc.is_contiguous()
+    L, R, Hkv, cap, hd = Kc.shape
+    assert parent.dtype == torch.int32 and parent.is_contiguous() and parent.numel() == R and n_dev.dtype == torch.int32
+    assert s0_dev is None or s0_dev.dtype == torch.int32
+    check(lib().gar_kv_beam_reorder(ptr(Kc), ptr(Vc), Kc.element_size(), L, R, int(K), Hkv, cap, hd, int(s0), ptr(s0_dev) or None,
+                                    ptr(n_dev), ptr(parent), stream()), "gar_kv_beam_reorder")

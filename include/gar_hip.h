@@ -605,6 +605,74 @@ int gar_sample_ext(int dtype, const void* logits, int64_t ld, int B, int V, int6
                    const int64_t* seed_dev, const int64_t* eos_ids, int n_eos, int32_t* finished, int32_t* done_count,
                    int row_offset, float* lp_raw, float* lp_warped, int32_t* n_kept, gar_stream_t stream);
 
+/* ---- Beam search (GARModel.generate(beam_search=BeamSearch(...))) -------------------------------------------------------
+ * Additive: two entry points, GAR_ABI_VERSION stays 16. Semantics: transformers' GenerationMixin._beam_search with do_sample=False
+ * (the reference forwards any GenerationConfig to HF's generate, modeling_gar.py:418-426), f32 arithmetic operation by operation.
+ * B prompts x K beams: rows b * K .. b * K + K - 1 belong to prompt b. K in 2..16, M in K..32, K * M <= 512; K and M fix the shapes
+ * of the buffers and the launch and are therefore host values, everything a request or a step changes is read from device memory, so
+ * one captured launch serves every step and every request of the same (B, K, M, T).
+ *
+ * gar_beam_step — one step t = step_dev[0] (NULL = 0; clamped to [0, T - 1]) of every prompt that is not done:
+ *   reads   top_ids int32 / top_lp f32 [B * K, M]: each row's M best raw log-probabilities as gar_topk_lp writes them (value
+ *           descending, index ascending; ids are clamped to [0, V - 1] before use); run_scores; params int32 [GAR_BEAM_PARAM_WORDS] =
+ *           {max_new_tokens (clamped to [1, T]), early_stopping (0 False, 1 True, 2 "never"), length_penalty > 0, n_eos (clamped to
+ *           [0, GAR_BEAM_MAX_EOS]), then the eos ids}; len_pow f32 [T], len_pow[i] = (float)((double)(i + 1) ** length_penalty).
+ *   candidates   score = run_scores[beam] + lp; the best M of the K * M by (score descending, beam ascending, token ascending) —
+ *                torch.topk leaves equal scores unspecified, this is gar_topk_lp's rule extended by the beam. A candidate hits the
+ *                stopping criteria at an eos id; every candidate does at t >= max_new_tokens - 1.
+ *   writes  run_scores f32 [B * K], parent int32 [B * K] (the sibling index 0..K-1 each new beam continues), cur_tokens int64 [B * K]:
+ *           the best K candidates by score + (-1e9 if hit), equal values by candidate rank;
+ *           hist int32 [2][B * K][T]: matrix (t + 1) & 1 takes columns 0..t-1 of matrix t & 1 gathered by parent and the new token at
+ *           column t (two matrices by step parity: no row is read after it was overwritten);
+ *           the finished set fin_tokens int32 [B * K][T], fin_scores f32, fin_len int32, fin_flag int32 [B * K], best first: the K kept
+ *           hypotheses followed by the M candidates at score / len_pow[t], - 1e9 once for each of {set full and early_stopping True,
+ *           heuristic latch off, not (hit and among the first K candidates)}, the best K by (score descending, position ascending). In
+ *           place: kept hypotheses only move towards the end, slots are filled last first. Columns above t are never written;
+ *           heur int32 [B]: latched &= any over slots of (best running score / len_pow[l]) > (slot finished ? least kept score : -1e9),
+ *           l = max_new_tokens - 1 with "never" and a positive penalty, else t;
+ *           done int32 [B] latched when the heuristic is off, the set is full under early_stopping True, or t >= max_new_tokens - 1;
+ *           done_count int32 [1] += newly done prompts. A prompt whose done latch is set on entry is not touched: a prompt's result
+ *           does not depend on its batch-mates.
+ *   Initial state (host): run_scores {0, -1e9, ...} per prompt, fin_scores -1e9, fin_tokens / fin_len / fin_flag / hist / done /
+ *   done_count 0, heur 1.
+ * Contract: one 512-thread workgroup per prompt; nothing in the planes or the state makes it read or write outside its prompt's rows
+ * (ids, parents, the step and the counts are clamped). Ranks are counted, so the result is deterministic; NaN scores are unspecified
+ * but stay in bounds. No allocation, no synchronisation, no cross-workgroup fence, hipGraph-capturable. */
+#define GAR_BEAM_MAX_EOS 16
+#define GAR_BEAM_PARAM_WORDS (4 + GAR_BEAM_MAX_EOS)
+typedef struct gar_beam_state {
+    const int32_t* top_ids;
+    const float* top_lp;
+    float* run_scores;
+    int64_t* cur_tokens;
+    int32_t* parent;
+    int32_t* hist;
+    int32_t* fin_tokens;
+    float* fin_scores;
+    int32_t* fin_len;
+    int32_t* fin_flag;
+    int32_t* heur;
+    int32_t* done;
+    int32_t* done_count;
+    const int32_t* params;
+    const float* len_pow;
+    const int32_t* step_dev;
+    int32_t B, K, M, T, V;
+} gar_beam_state;
+int gar_beam_step(const gar_beam_state* state, gar_stream_t stream);
+
+/* gar_kv_beam_reorder — the caches follow the beams: for every layer, both caches, every prompt b, kv head, position
+ * s0 .. s0 + n - 1 and sibling j, row b * K + j of Kc / Vc [L, R, Hkv, cap, hd] takes the bytes of row b * K + parent[b * K + j]
+ * (parent clamped to [0, K - 1]). n = n_dev[0] and s0 (s0_dev[0] when s0_dev is not NULL, else the argument) are clamped to the
+ * capacity: 0 <= s0 <= cap, 0 <= n <= cap - s0; positions outside the range keep their bytes, bytes moved grow with n.
+ * elem_size 2 or 4 (hd * elem_size a multiple of 16, caches 16-byte aligned): bytes are moved, not values.
+ * Contract: ONE launch, in place: a thread owns one 16-byte chunk of one position for the K siblings and loads every chunk a moved
+ * sibling takes before it stores any, so cycles of parents are safe and no second cache exists; rows with parent[j] == j are neither
+ * loaded nor stored, a prompt whose parents are the identity moves nothing. No allocation, no synchronisation, no cross-workgroup
+ * fence, hipGraph-capturable, deterministic. */
+int gar_kv_beam_reorder(void* Kc, void* Vc, int elem_size, int L, int R, int K, int Hkv, int cap, int hd, int s0,
+                        const int32_t* s0_dev, const int32_t* n_dev, const int32_t* parent, gar_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
