@@ -1144,24 +1144,24 @@ extern "C" int gar_topk_lp(int dtype, const void* logits, int64_t ld, int B, int
 // every read of the history by out_cols, every marked id by V.
 // ---------------------------------------------------------------------------------------------------------------
 #define LP_THREADS 1024
-#define LP_HEADER 8                 // params: [penalty f32 bits, n, m, n_suppress, n_begin, n_bad, n_bad_tokens, 0] then the lists
+#define LP_HEADER 8                 // params: [penalty f32 bits, n, m, n_suppress, n_begin, n_bad, n_bad_tokens, col0] then the lists
+#define LP_COL0 7                   // gar_logits_process_rows only: the token column of the row's step 0 (gar_logits_process never reads it)
 #define LP_MAX_VOCAB 262144         // two bitmaps in 64 KB of LDS
 
+// One row under one parameter block — the body of both entry points, run by the row's whole workgroup: `row` the row's logits, `hist`
+// its t generated tokens (never dereferenced at t = 0), `params` its block, read within params_words. gar_logits_process hands every
+// row the call's one block and the history at columns 0 .. t-1; gar_logits_process_rows hands row b its own block and the history
+// that starts at the block's col0.
 template <typename T>
-__global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(T* __restrict__ logits, int64_t ld, int V,
-                                                                    const int64_t* __restrict__ out_tokens, int64_t out_stride,
-                                                                    int out_cols, const int32_t* __restrict__ step_dev,
-                                                                    const int64_t* __restrict__ eos_ids, int n_eos,
-                                                                    const int32_t* __restrict__ params, int params_words) {
+__device__ __forceinline__ void logits_process_row(T* __restrict__ row, int V, const int64_t* __restrict__ hist, int t,
+                                                   const int64_t* __restrict__ eos_ids, int n_eos,
+                                                   const int32_t* __restrict__ params, int params_words) {
     extern __shared__ unsigned int lp_bits[];
     const int W = (V + 31) >> 5;
     unsigned int* pen = lp_bits;
     unsigned int* ban = lp_bits + W;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     for (int w = tid; w < 2 * W; w += LP_THREADS) lp_bits[w] = 0u;
-    int t = step_dev ? step_dev[0] : 0;
-    t = out_tokens ? max(0, min(t, out_cols)) : 0;
-    const int64_t* hist = out_tokens + (int64_t)b * out_stride;
     const float p = __int_as_float(params[0]);
     const int n = params[1], m = params[2];
     int n_sup = params[3], n_beg = params[4], n_bad = params[5], n_bt = params[6];
@@ -1200,7 +1200,6 @@ __global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(T* __restric
         if (same) mark(ban, bad_tok[o1 - 1]);
     }
     __syncthreads();
-    T* row = logits + (int64_t)b * ld;
     for (int w = tid; w < W; w += LP_THREADS) {
         const unsigned int bw = ban[w];
         unsigned int bits = pen[w] | bw;
@@ -1218,26 +1217,68 @@ __global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(T* __restric
     }
 }
 
+// ROWS = false (gar_logits_process): one block for every row, a row's step is the shared step and its history starts at column 0.
+// ROWS = true (gar_logits_process_rows, ContinuousBatcher(processing=True)): params is [B][params_words], row b its own block. A block
+// whose word 0 is 0 — no penalty's f32 bits are: pack() writes a penalty > 0 — is a row without a request, left before anything is
+// read or written (one word, the same for the whole workgroup, in front of the body's barriers). Word LP_COL0 is the column of the
+// token matrix at which the row's step 0 was written: with the shared column c the row's step is c - col0 and its history
+// out_tokens[b][col0 .. c-1]; columns in front of col0 belong to retired captions and are never read.
+template <typename T, bool ROWS>
+__global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(T* __restrict__ logits, int64_t ld, int V,
+                                                                    const int64_t* __restrict__ out_tokens, int64_t out_stride,
+                                                                    int out_cols, const int32_t* __restrict__ step_dev,
+                                                                    const int64_t* __restrict__ eos_ids, int n_eos,
+                                                                    const int32_t* __restrict__ params, int params_words) {
+    const int b = blockIdx.x;
+    if (ROWS) {
+        params += (int64_t)b * params_words;
+        if (params[0] == 0) return;
+    }
+    int t = step_dev ? step_dev[0] : 0;
+    t = out_tokens ? max(0, min(t, out_cols)) : 0;
+    const int64_t* hist = out_tokens + (int64_t)b * out_stride;
+    if (ROWS) {
+        const int col0 = max(0, min(params[LP_COL0], t));
+        hist += col0;
+        t -= col0;
+    }
+    logits_process_row<T>(logits + (int64_t)b * ld, V, hist, t, eos_ids, n_eos, params, params_words);
+}
+
 extern "C" int gar_logits_process_max_vocab(void) { return LP_MAX_VOCAB; }
+
+template <bool ROWS>
+static int logits_process_launch(const char* who, int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens,
+                                 int64_t out_stride, int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos,
+                                 const int32_t* params_dev, int params_words, gar_stream_t stream) {
+    GAR_CHECK_ARG(logits && params_dev && B > 0 && V > 0 && ld >= V, "%s: bad args", who);
+    GAR_CHECK_ARG(V <= LP_MAX_VOCAB, "%s: V %d above %d (two vocabulary bitmaps in 64 KB of LDS)", who, V, LP_MAX_VOCAB);
+    GAR_CHECK_ARG(params_words >= LP_HEADER, "%s: a parameter block of %d words, the header alone has %d", who, params_words, LP_HEADER);
+    GAR_CHECK_ARG(!out_tokens || (out_cols >= 0 && out_stride >= out_cols), "%s: out_cols %d / out_stride %lld", who, out_cols,
+                  (long long)out_stride);
+    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids), "%s: eos_ids", who);
+    const size_t lds = (size_t)((V + 31) >> 5) * 8;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GAR_BF16)
+        hipLaunchKernelGGL((logits_process_kernel<bf16_t, ROWS>), dim3(B), dim3(LP_THREADS), lds, s, (bf16_t*)logits, ld, V, out_tokens,
+                           out_stride, out_cols, step_dev, eos_ids, n_eos, params_dev, params_words);
+    else
+        hipLaunchKernelGGL((logits_process_kernel<float, ROWS>), dim3(B), dim3(LP_THREADS), lds, s, (float*)logits, ld, V, out_tokens,
+                           out_stride, out_cols, step_dev, eos_ids, n_eos, params_dev, params_words);
+    GAR_CHECK_LAUNCH();
+    return GAR_OK;
+}
 
 extern "C" int gar_logits_process(int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens, int64_t out_stride,
                                   int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos,
                                   const int32_t* params_dev, int params_words, gar_stream_t stream) {
-    GAR_CHECK_ARG(logits && params_dev && B > 0 && V > 0 && ld >= V, "logits_process: bad args");
-    GAR_CHECK_ARG(V <= LP_MAX_VOCAB, "logits_process: V %d above %d (two vocabulary bitmaps in 64 KB of LDS)", V, LP_MAX_VOCAB);
-    GAR_CHECK_ARG(params_words >= LP_HEADER, "logits_process: a parameter block of %d words, the header alone has %d", params_words,
-                  LP_HEADER);
-    GAR_CHECK_ARG(!out_tokens || (out_cols >= 0 && out_stride >= out_cols), "logits_process: out_cols %d / out_stride %lld", out_cols,
-                  (long long)out_stride);
-    GAR_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids), "logits_process: eos_ids");
-    const size_t lds = (size_t)((V + 31) >> 5) * 8;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == GAR_BF16)
-        hipLaunchKernelGGL(logits_process_kernel<bf16_t>, dim3(B), dim3(LP_THREADS), lds, s, (bf16_t*)logits, ld, V, out_tokens,
-                           out_stride, out_cols, step_dev, eos_ids, n_eos, params_dev, params_words);
-    else
-        hipLaunchKernelGGL(logits_process_kernel<float>, dim3(B), dim3(LP_THREADS), lds, s, (float*)logits, ld, V, out_tokens,
-                           out_stride, out_cols, step_dev, eos_ids, n_eos, params_dev, params_words);
-    GAR_CHECK_LAUNCH();
-    return GAR_OK;
+    return logits_process_launch<false>("logits_process", dtype, logits, ld, B, V, out_tokens, out_stride, out_cols, step_dev, eos_ids,
+                                        n_eos, params_dev, params_words, stream);
+}
+
+extern "C" int gar_logits_process_rows(int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens,
+                                       int64_t out_stride, int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos,
+                                       const int32_t* row_params, int row_words, gar_stream_t stream) {
+    return logits_process_launch<true>("logits_process_rows", dtype, logits, ld, B, V, out_tokens, out_stride, out_cols, step_dev,
+                                       eos_ids, n_eos, row_params, row_words, stream);
 }

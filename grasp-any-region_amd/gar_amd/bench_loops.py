@@ -57,6 +57,11 @@ def base_parser(description, default_model, default_cache, default_images):
     ap.add_argument("--temperature", type=float, default=None, help="with --do_sample (default: HF's 1.0)")
     ap.add_argument("--top_k", type=int, default=None, help="with --do_sample (default: HF's 50; 0 = off)")
     ap.add_argument("--top_p", type=float, default=None, help="with --do_sample (default: HF's 1.0 = off)")
+    ap.add_argument("--repetition_penalty", type=float, default=None,
+                    help="with --continuous: every item runs under HF's repetition penalty (> 0; 1.0 = off) over its own caption, on "
+                         "the device (ContinuousBatcher(processing=True))")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=None,
+                    help="with --continuous: no n-gram of this size repeats within an item's caption (0 = off)")
     ap.add_argument("--kv_cache_dtype", choices=("auto", "fp8"), default="auto",
                     help="decode KV cache: auto = the model dtype; fp8 = OCP e4m3 with one scale per vector (16-bit models only)")
     ap.add_argument("--decode_weight_dtype", choices=("auto", "fp8"), default="auto",
@@ -98,6 +103,7 @@ def write_run_meta(path, args, model):
     meta = {"batch_size": int(getattr(args, "batch_size", 1) or 1), "continuous": bool(getattr(args, "continuous", False)),
             **({"do_sample": True, "seed": args.seed, "temperature": args.temperature, "top_k": args.top_k, "top_p": args.top_p}
                if getattr(args, "do_sample", False) else {}),
+            **({"logits_processing": processing_options(args)} if processing_options(args) else {}),
             "data_type": args.data_type,
             "max_num_tiles": args.max_num_tiles, "max_new_tokens": args.max_new_tokens,
             "synthetic_weights": bool(args.synthetic_weights), "host_preprocessing": bool(args.host_preprocessing),
@@ -106,6 +112,11 @@ def write_run_meta(path, args, model):
                                                                  "PRUNE_LAST_PREFILL_LAYER") if hasattr(model, k)},
             "abi_version": hip_abi_version()}
     json.dump(meta, open(os.path.splitext(path)[0] + ".meta.json", "w"), indent=2)
+
+
+def processing_options(args) -> dict:
+    """--repetition_penalty / --no_repeat_ngram_size as the fields of a LogitsProcessing; empty when neither is given"""
+    return {k: getattr(args, k) for k in ("repetition_penalty", "no_repeat_ngram_size") if getattr(args, k, None) is not None}
 
 
 def hip_abi_version():
@@ -215,10 +226,15 @@ class ContinuousRunner:
         if getattr(args, "do_sample", False):
             self.options = dict(do_sample=True, **{k: getattr(args, k) for k in ("temperature", "top_k", "top_p")
                                                    if getattr(args, k, None) is not None})
+        # --repetition_penalty / --no_repeat_ngram_size: every item's own logits processing (neutral values: a loop without)
+        from .logits_processing import LogitsProcessing
+        self.processing = LogitsProcessing.coerce(processing_options(args))
+        self.processing = None if self.processing.neutral else self.processing
         self.seed0 = int(getattr(args, "seed", 0) or 0)
         self.cb = ContinuousBatcher(model, slots=max(2, int(args.batch_size)), max_new_tokens=args.max_new_tokens,
                                     eos_token_id=tk.eos_token_id, poll_every=getattr(args, "poll_every", 8),
-                                    **({} if self.options is None else dict(sampling=True)))
+                                    **({} if self.options is None else dict(sampling=True)),
+                                    **({} if self.processing is None else dict(processing=True)))
         self.pending = {}
         self.results = []
         self.items = 0
@@ -232,10 +248,11 @@ class ContinuousRunner:
             self.results.append((idx, finish(text)))
 
     def add(self, idx, sample, finish):
+        proc = {} if self.processing is None else dict(logits_processing=self.processing)
         if self.options is None:
-            ticket = self.cb.submit(sample)
+            ticket = self.cb.submit(sample, **proc)
         else:
-            ticket = self.cb.submit(sample, seed=self.seed0 + self.items, **self.options)
+            ticket = self.cb.submit(sample, seed=self.seed0 + self.items, **self.options, **proc)
         self.pending[ticket] = (idx, finish)
         self.items += 1
         self.cb.pump()
@@ -255,6 +272,8 @@ def make_runner(model, processor, args, skip_special_tokens):
         return ContinuousRunner(model, processor, args, skip_special_tokens)
     if getattr(args, "do_sample", False):
         raise SystemExit("--do_sample is implemented with --continuous --batch_size n > 1 only (the other loops are greedy)")
+    if processing_options(args):
+        raise SystemExit("--repetition_penalty / --no_repeat_ngram_size are implemented with --continuous --batch_size n > 1 only")
     return Batcher(model, processor, args, skip_special_tokens)
 
 

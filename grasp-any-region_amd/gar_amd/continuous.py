@@ -27,7 +27,12 @@ f32 identical, in bf16 up to the batch-size dependent kernel selection INTEGRATI
   row (:func:`pack_sample_row`): greedy or sampled, temperature / top-k / top-p, the Philox key, and ``col0`` — the column of
   the token log the row's caption started at. The shared step counter is a column of that log, not any row's step;
   ``gar_sample_rows`` reads the row's step as ``column - col0``, so one captured graph serves a batch in which every row samples,
-  or does not, under its own request, and a sampled ticket draws what ``generate(do_sample=True, seed=...)`` draws for it alone."""
+  or does not, under its own request, and a sampled ticket draws what ``generate(do_sample=True, seed=...)`` draws for it alone.
+* **per-request logits processing** (``processing=True``). The decode state then carries one parameter block per row
+  (:func:`pack_process_row`: ``LogitsProcessing.pack``'s words with header word 7 = ``col0``); ``gar_logits_process_rows`` runs in
+  front of the pick, reads a row's history from ``col0`` on and leaves a row with a zero header — a free row, a ticket without
+  processing — alone. ``submit(sample, logits_processing=...)`` gives a ticket its own penalties and bans, and its tokens are those of
+  ``generate(logits_processing=...)`` on that region alone."""
 from __future__ import annotations
 
 import struct
@@ -37,7 +42,11 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import hip
+from .logits_processing import HEADER_WORDS as PROCESS_HEADER_WORDS, LogitsProcessing, _Refused as _ProcessingRefused
+from .ops import LOGITS_PROCESS_WORDS    # gar_logits_process_rows: int32 words of one row's parameter block
 from .ops import SAMPLE_ROW_WORDS        # gar_sample_rows: int32 words of one row's request (include/gar_hip.h)
+
+PROCESS_COL0_WORD = 7                    # header word of a row's block that holds col0 (0 in generate()'s one block)
 
 
 def _round_up(x, m):
@@ -84,11 +93,28 @@ def pack_sample_row(sampling, seed, col0: int, counter_row: int = 0, mode: Optio
     return [1, _f32_bits(temperature), _f32_bits(top_p), int(top_k), _i32(seed), _i32(seed >> 32), col0, counter_row]
 
 
-class _Row:
-    __slots__ = ("ticket", "start_col", "left_pad", "n_prompt", "tokens", "fresh")
+def pack_process_row(proc: Optional[LogitsProcessing], vocab_size: int, eos_ids, col0: int) -> List[int]:
+    """The int32 words of one row's parameter block as ``gar_logits_process_rows`` reads them: ``proc.pack(vocab_size, eos_ids)``
+    with header word 7 set to ``col0``, the token column of the row's step 0. ``proc`` None — a row without a request — gives the
+    all-zero header (word 0 = 0 is what the kernel leaves a row alone by; ``pack`` never writes it, the f32 bits of a penalty > 0).
+    ``pack``'s refusals (an id outside the vocabulary, more words than the block holds) come through as they are raised."""
+    col0 = int(col0)
+    if not -2 ** 31 <= col0 < 2 ** 31:
+        raise ValueError(f"col0 {col0} outside an int32")
+    if proc is None:
+        return [0] * PROCESS_HEADER_WORDS
+    words = proc.pack(vocab_size, eos_ids)
+    assert words[0] != 0 and words[PROCESS_COL0_WORD] == 0
+    words[PROCESS_COL0_WORD] = col0
+    return words
 
-    def __init__(self, ticket, start_col, left_pad, n_prompt):
+
+class _Row:
+    __slots__ = ("ticket", "start_col", "left_pad", "n_prompt", "tokens", "fresh", "processed")
+
+    def __init__(self, ticket, start_col, left_pad, n_prompt, processed=False):
         self.ticket, self.start_col, self.left_pad, self.n_prompt = ticket, start_col, left_pad, n_prompt
+        self.processed = processed   # the row's block in st["row_proc"] holds a request (its col0 moves with the token log)
         self.tokens: List[int] = []
         self.fresh = True            # admitted since the last poll: its first token sits one column in front of the new ones
 
@@ -105,15 +131,15 @@ class ContinuousBatcher:
                  admit_min: Optional[int] = None, lookahead: Optional[int] = None, horizon: Optional[int] = None,
                  validate: bool = True, use_graph: bool = True, smax_multiple: int = 256, return_logprobs: bool = False,
                  top_logprobs: int = 0, candidate_token_ids=None, logits_processing=None, sampling: bool = False,
-                 sampling_warpers=None):
+                 sampling_warpers=None, processing: bool = False):
         if sampling_warpers is not None:
             # a row's request is eight words (gar_sample_rows, SAMPLE_ROW_WORDS) and all eight are taken: the four warpers have no
             # place in it yet
             raise hip.GarError("ContinuousBatcher: sampling_warpers is not implemented (call generate(sampling_warpers=...))")
         if logits_processing is not None:
-            # the processors read a row's history from columns 0..t-1 of the token matrix; this loop shifts that matrix per row
-            # (_rebase), so a row's column is not its step: not threaded through here
-            raise hip.GarError("ContinuousBatcher: logits_processing is not implemented (call generate(logits_processing=...))")
+            # processing is a ticket's own: a batcher-wide value has no place among rows that each carry a block
+            raise hip.GarError("ContinuousBatcher: a batcher-wide logits_processing is not implemented — build the batcher with "
+                               "processing=True and pass submit(sample, logits_processing=...) per ticket")
         if top_logprobs or candidate_token_ids:
             # generate()'s [rows, T, k] planes are addressed by the step's column like the token matrix this loop shifts (_rebase),
             # and pop_finished returns token lists only: not threaded through here
@@ -148,6 +174,10 @@ class ContinuousBatcher:
         # with gar_sample_rows. False: the state, the graph key and the launches of the greedy-only loop
         self.sampling = bool(sampling)
         self._requests: Dict[int, tuple] = {}                # ticket -> ((temperature, top_p, top_k), seed) of a sampled ticket
+        # per-request logits processing: the decode state carries a parameter block per row and the step runs
+        # gar_logits_process_rows in front of its pick. False: the state, the graph key and the launches of the loop without
+        self.processing = bool(processing)
+        self._processing: Dict[int, LogitsProcessing] = {}   # ticket -> its non-neutral LogitsProcessing, until admission
         self.seeds: Dict[int, int] = {}                      # ticket -> Philox key, every sampled ticket
         self.smax_multiple = max(64, _round_up(int(smax_multiple), 64))      # cache rows come in buckets (graph / state reuse)
         self.queue: deque = deque()
@@ -165,27 +195,34 @@ class ContinuousBatcher:
 
     # ---- queue ------------------------------------------------------------------------------------------------------
     def submit(self, sample: dict, generation_config=None, seed: Optional[int] = None, sampling_warpers=None,
-               beam_search=None, **generate_kwargs) -> int:
+               beam_search=None, logits_processing=None, **generate_kwargs) -> int:
         """queue one region. The generation options are read as ``generate`` reads them (a GenerationConfig / dict with the
         keyword arguments laid over it; HF's defaults, so ``top_k`` 50): ``do_sample=True`` — on a batcher built with
         ``sampling=True`` — makes this ticket a sampled one under its own temperature / top_k / top_p and ``seed`` (None: drawn
-        as ``generate`` draws it; recorded in ``seeds[ticket]``). ``max_new_tokens`` and ``eos_token_id`` stay per batcher."""
+        as ``generate`` draws it; recorded in ``seeds[ticket]``). ``logits_processing`` (a :class:`LogitsProcessing` or a dict of
+        its fields) — on a batcher built with ``processing=True`` — gives this ticket its own repetition penalty, n-gram ban,
+        ``min_new_tokens``, suppress lists and bad words, as ``generate(logits_processing=...)`` applies them; None or all-neutral
+        values are a ticket without. ``max_new_tokens`` and ``eos_token_id`` stay per batcher."""
         if int(sample["input_ids"].shape[0]) != 1:
             raise ValueError("ContinuousBatcher.submit takes one region per sample (input_ids [1, S])")
         if sample.get("top_logprobs") or sample.get("candidate_token_ids"):
             raise hip.GarError("ContinuousBatcher.submit: top_logprobs / candidate_token_ids are not implemented (call "
                                "generate(top_logprobs=..., candidate_token_ids=...))")
         if sample.get("logits_processing") is not None:
-            raise hip.GarError("ContinuousBatcher.submit: logits_processing is not implemented (call generate(logits_processing=...))")
+            raise hip.GarError("ContinuousBatcher.submit: a logits_processing key inside the sample is not implemented — pass "
+                               "submit(sample, logits_processing=...) on a batcher built with processing=True")
         if sampling_warpers is not None or sample.get("sampling_warpers") is not None:
             raise hip.GarError("ContinuousBatcher.submit: sampling_warpers is not implemented (call generate(sampling_warpers=...))")
         if sample.get("return_logprobs"):
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
         if beam_search is not None or sample.get("beam_search") is not None:
             raise hip.GarError("ContinuousBatcher.submit: beam_search is not implemented (call generate(beam_search=...))")
+        proc = self._read_processing(logits_processing)      # (in front of the options: a refused request draws no seed)
         request = self._read_options(generation_config, generate_kwargs, seed)
         t = self._next_ticket
         self._next_ticket += 1
+        if proc is not None:
+            self._processing[t] = proc
         if request is not None:
             self._requests[t] = request
             self.seeds[t] = request[1]
@@ -220,6 +257,30 @@ class ContinuousBatcher:
         seed = _draw_seed() if seed is None else int(seed)
         pack_sample_row(sampling, seed, 0)                   # (a seed outside [0, 2**63) is refused here, not at admission)
         return sampling, seed
+
+    def _read_processing(self, logits_processing) -> Optional[LogitsProcessing]:
+        """the ticket's LogitsProcessing, None for a neutral one; everything that admission would refuse is refused here, so a
+        refused request takes no ticket"""
+        proc = LogitsProcessing.coerce(logits_processing)
+        if proc.neutral:
+            return None
+        if not self.processing:
+            raise hip.GarError("ContinuousBatcher.submit: logits_processing needs a batcher built with ContinuousBatcher(..., "
+                               "processing=True)")
+        from . import ops
+        V = int(self.model.config.mllm_config.text_config.vocab_size)
+        if V > ops.logits_process_max_vocab():
+            raise hip.GarError(f"logits_processing: vocab_size {V} above gar_logits_process's {ops.logits_process_max_vocab()}")
+        if proc.min_new_tokens and len(self.eos) > self.model.MAX_EOS_IDS:
+            raise hip.GarError(f"logits_processing: min_new_tokens with {len(self.eos)} eos ids: the device-side eos table holds "
+                               f"{self.model.MAX_EOS_IDS}")
+        try:
+            words = pack_process_row(proc, V, self.eos, 0)
+        except _ProcessingRefused as e:
+            raise hip.GarError(str(e)) from None
+        if len(words) > LOGITS_PROCESS_WORDS:
+            raise hip.GarError(f"logits_processing: {len(words)} words, a row's block holds {LOGITS_PROCESS_WORDS}")
+        return proc
 
     def pump(self):
         """advance while more than ``lookahead`` regions are waiting (call after submit: keeps the queue bounded)"""
@@ -293,6 +354,8 @@ class ContinuousBatcher:
             st["left_pad"].index_fill_(0, idx, self.Smax - 1)
             if self.sampling:                # ... and its request: a free row is a greedy row that draws nothing
                 st["row_words"].index_fill_(0, idx, 0)
+            if self.processing:              # ... and its block's header: a free row is a row without processing
+                st["row_proc"][:, :PROCESS_HEADER_WORDS].index_fill_(0, idx, 0)
             for r in retire:
                 self.rows[r] = None
             self.stats["retired"] += len(retire)
@@ -360,10 +423,14 @@ class ContinuousBatcher:
             self.out_tokens = m._buf(self.skey, "out_tokens", (self.B, self.Smax), torch.int64, zero=True)
             if self.sampling:
                 self.st["row_words"] = m._buf(self.skey, "row_words", (self.B, SAMPLE_ROW_WORDS), torch.int32, zero=True)
+            if self.processing:
+                self.st["row_proc"] = m._buf(self.skey, "row_proc", (self.B, LOGITS_PROCESS_WORDS), torch.int32, zero=True)
             self.graph = None
         st = self.st
         if self.sampling:
             st["row_words"].zero_()
+        if self.processing:
+            st["row_proc"].zero_()
         st["eos_ids"].fill_(-1)
         if self.eos:
             st["eos_ids"][:len(self.eos)].copy_(torch.tensor(self.eos, dtype=torch.int64, device=m.device))
@@ -416,6 +483,12 @@ class ContinuousBatcher:
             # sample alone draws; in the staging state a caption starts at column 0
             reqs = [self._requests.pop(t, (None, None)) for t, _ in group]
             batch["_row_words"] = [pack_sample_row(sampling, seed, 0) for sampling, seed in reqs]
+        if self.processing:
+            # the group's blocks: the first token is a row's step 0 (begin_suppress_tokens, min_new_tokens, suppress_tokens and
+            # one-token bad words act on it), written at column 0 of the staging state
+            procs = [self._processing.pop(t, None) for t, _ in group]
+            V = int(m.config.mllm_config.text_config.vocab_size)
+            batch["_row_proc"] = [pack_process_row(p, V, self.eos, 0) for p in procs]
         pend = m.generate_begin(**batch, max_new_tokens=1, eos_token_id=self.eos or None, state_slot=self.STAGE_SLOT,
                                 validate=self.validate)
         if not self.validate:
@@ -439,13 +512,17 @@ class ContinuousBatcher:
         if self.sampling:                    # the rows' requests, their step 0 at the column the first token goes to
             words = [pack_sample_row(sampling, seed, T - 1) for sampling, seed in reqs]
             st["row_words"].index_copy_(0, rows_t, torch.tensor(words, dtype=torch.int32, device=dev))
+        if self.processing:                  # the rows' blocks, their histories from the column the first token goes to
+            from .modeling_gar import _process_blocks
+            blocks = _process_blocks([pack_process_row(p, V, self.eos, T - 1) for p in procs])
+            st["row_proc"].index_copy_(0, rows_t, blocks.to(dev))
         self.out_tokens[rows_t, T - 1] = first
         # first token already an eos id: latched at the column it was written to
         fin0 = torch.where(sg["finished"][:G] >= 0, torch.full((G,), T - 1, dtype=torch.int32, device=dev),
                            torch.full((G,), -1, dtype=torch.int32, device=dev))
         st["finished"].index_copy_(0, rows_t, fin0)
         for i, r in enumerate(rows):
-            self.rows[r] = _Row(group[i][0], T - 1, offs[i], lens[i])
+            self.rows[r] = _Row(group[i][0], T - 1, offs[i], lens[i], self.processing and procs[i] is not None)
         self.stats["prompt_passes"] += 1
         self.stats["admitted"] += G
 
@@ -477,6 +554,12 @@ class ContinuousBatcher:
         idx = torch.tensor([r for r, _ in live], dtype=torch.int64, device=self.model.device)
         if dT > 0 and self.sampling:         # col0 moves with the token log (free rows hold zeros and draw nothing)
             st["row_words"][:, 6].index_add_(0, idx, torch.full((len(live),), -dT, dtype=torch.int32, device=self.model.device))
+        if dT > 0 and self.processing:       # ... and so does the col0 of every live row that carries a request
+            pidx = [r for r, row in live if row.processed]
+            if pidx:
+                st["row_proc"][:, PROCESS_COL0_WORD].index_add_(0, torch.tensor(pidx, dtype=torch.int64, device=self.model.device),
+                                                                torch.full((len(pidx),), -dT, dtype=torch.int32,
+                                                                           device=self.model.device))
         lp = torch.tensor([row.left_pad for _, row in live], dtype=torch.int32, device=self.model.device)
         st["left_pad"].index_copy_(0, idx, lp)
         # live rows are running (their latches are -1); free rows' latches are reset at admission

@@ -74,8 +74,9 @@ class GenerateOutput:
 class _PickTargets(NamedTuple):
     """where a pick (GARModel._pick) writes: the token matrix, the current tokens and the eos latches of its rows, the batch row of
     its first row (the Philox row counter of a draw), the (raw, warped) log-probability planes of a return_logprobs request or
-    None, the planes of a top_logprobs / candidate_token_ids request (GARModel._topk_planes) or None, and the rows' own request
-    words (int32 [rows, 8], gar_sample_rows) of a state that carries them or None."""
+    None, the planes of a top_logprobs / candidate_token_ids request (GARModel._topk_planes) or None, the rows' own request
+    words (int32 [rows, 8], gar_sample_rows) of a state that carries them or None, and the rows' own processing blocks (int32
+    [rows, LOGITS_PROCESS_WORDS], gar_logits_process_rows) of a state that carries them or None."""
     out_tokens: torch.Tensor
     cur: torch.Tensor
     finished: torch.Tensor
@@ -83,17 +84,27 @@ class _PickTargets(NamedTuple):
     lp: Optional[tuple]
     tk: Optional[dict]
     row_words: Optional[torch.Tensor] = None
+    row_proc: Optional[torch.Tensor] = None
 
     @classmethod
     def of(cls, st, out_tokens) -> "_PickTargets":          # every row of a state
-        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"), st.get("row_words"))
+        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"), st.get("row_words"), st.get("row_proc"))
 
     def rows(self, r0: int, r1: int) -> "_PickTargets":
         """cut to rows r0 .. r1 - 1: a prompt chunk's first-token head"""
         tk = self.tk and dict(self.tk, **{n: self.tk[n][r0:r1] for n in ("ids", "lp", "cand_lp") if self.tk[n] is not None})
         return _PickTargets(self.out_tokens[r0:r1], self.cur[r0:r1], self.finished[r0:r1], self.row0 + r0,
                             self.lp and tuple(p[r0:r1] for p in self.lp), tk,
-                            None if self.row_words is None else self.row_words[r0:r1])
+                            None if self.row_words is None else self.row_words[r0:r1],
+                            None if self.row_proc is None else self.row_proc[r0:r1])
+
+
+def _process_blocks(rows) -> torch.Tensor:
+    """host int32 [len(rows), LOGITS_PROCESS_WORDS]: every row's words (continuous.pack_process_row) in front, zeros behind"""
+    blocks = torch.zeros((len(rows), ops.LOGITS_PROCESS_WORDS), dtype=torch.int32)
+    for b, words in enumerate(rows):
+        blocks[b, :len(words)] = torch.tensor(words, dtype=torch.int32)
+    return blocks
 
 
 def logprob_outputs(raw: torch.Tensor, warped: torch.Tensor, finished_at: Sequence[Optional[int]]):
@@ -1392,15 +1403,23 @@ class GARModel:
             self._pick(logits, V, st, to)
         return logits
 
-    def _process(self, logits, V, st, out_tokens):
+    def _process(self, logits, V, st, out_tokens, row_proc=None):
         """the request's logits processors on ``logits`` in place (one gar_logits_process launch), the rows' histories read from
-        ``out_tokens`` up to the state's step; nothing — no launch — for a request without a non-neutral ``logits_processing``"""
-        if st.get("proc") is not None:
-            if out_tokens is not None:
-                # out_tokens is a [:, :max_new_tokens] slice of the state's token buffer; the captured step serves every
-                # max_new_tokens of the bucket, so the history's bound is the buffer's row (its stride), not the slice's width
-                cap = out_tokens.stride(0)
-                out_tokens = out_tokens.as_strided((out_tokens.shape[0], cap), (cap, 1), out_tokens.storage_offset())
+        ``out_tokens`` up to the state's step; nothing — no launch — for a request without a non-neutral ``logits_processing``.
+        ``row_proc`` (ContinuousBatcher(processing=True)): the rows' own blocks instead, one gar_logits_process_rows launch — a row's
+        history starts at its block's ``col0``, a row with a zero header is left alone."""
+        if st.get("proc") is None and row_proc is None:
+            return
+        if st.get("proc") is not None and row_proc is not None:
+            raise hip.GarError("per-row processing blocks and a logits_processing of the call's own do not combine")
+        if out_tokens is not None:
+            # out_tokens is a [:, :max_new_tokens] slice of the state's token buffer; the captured step serves every
+            # max_new_tokens of the bucket, so the history's bound is the buffer's row (its stride), not the slice's width
+            cap = out_tokens.stride(0)
+            out_tokens = out_tokens.as_strided((out_tokens.shape[0], cap), (cap, 1), out_tokens.storage_offset())
+        if row_proc is not None:
+            ops.logits_process_rows(logits, V, out_tokens, st["counters"][2:3], st["eos_ids"], row_proc)
+        else:
             ops.logits_process(logits, V, out_tokens, st["counters"][2:3], st["eos_ids"], st["proc"])
 
     def _arm_processing(self, skey, st, proc: Optional[LogitsProcessing], eos_list, eos_on_device: bool):
@@ -1430,14 +1449,17 @@ class GARModel:
         (gar_argmax) — with log-probability planes the launch that also writes the chosen token's (gar_sample_lp / gar_argmax_lp); a
         sampled request with sampling_warpers draws with gar_sample_ext in gar_sample's place.
         A state whose rows carry requests of their own (``to.row_words``: ContinuousBatcher(sampling=True)) picks every row with
-        gar_sample_rows instead."""
+        gar_sample_rows instead; one whose rows carry processing blocks of their own (``to.row_proc``: ContinuousBatcher(
+        processing=True)) runs gar_logits_process_rows in front of that pick, or of the greedy one."""
         B, tk, step = logits.shape[0], to.tk, st["counters"][2:3]
         key = ("head", B, st.get("slot", 0))
         if st.get("beam") is not None:      # beam_search: the rows' M best, the beams' bookkeeping, the caches behind their parents
             self._beam_pick(logits, V, st, key)
             return
+        if to.row_proc is not None and (to.lp is not None or tk is not None):
+            raise hip.GarError("per-row processing blocks carry no log-probability planes (they are defined over the unprocessed logits)")
         if process:
-            self._process(logits, V, st, to.out_tokens)
+            self._process(logits, V, st, to.out_tokens, to.row_proc)
         if tk is not None:
             ws = self._buf(key, f"tkws{tk['k']}", (ops.topk_lp_workspace(B, V, tk["k"]),), torch.uint8)   # by k: a captured step keeps its own
             ops.topk_lp(logits, V, step, ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"], cand_lp=tk["cand_lp"])
@@ -1445,7 +1467,8 @@ class GARModel:
         latches = dict(eos_ids=st["eos_ids"], finished=to.finished, done_count=st["done_count"], logprobs=raw, logprobs_warped=warped)
         if to.row_words is not None:
             if to.lp is not None or tk is not None or st.get("proc") is not None or st.get("sampling"):
-                raise hip.GarError("per-row sampling requests carry no log-probability planes and no logits processing")
+                raise hip.GarError("per-row sampling requests carry no log-probability planes and no logits_processing of the "
+                                   "call's own (a row's processing goes in its block: _row_proc)")
             ops.sample_rows(logits, V, to.out_tokens, to.out_tokens.stride(0), step, to.cur, to.row_words, eos_ids=st["eos_ids"],
                             finished=to.finished, done_count=st["done_count"])
         elif st.get("sampling") and st.get("warpers"):          # sampling_warpers: the same pick through gar_sample_ext
@@ -1798,7 +1821,8 @@ class GARModel:
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
                        top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None, logits_processing=None,
-                       sampling_warpers=None, beam_search=None, _row_words=None, **generate_kwargs) -> "_PendingGeneration":
+                       sampling_warpers=None, beam_search=None, _row_words=None, _row_proc=None,
+                       **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
         the request; None draws one from torch's global generator).
@@ -1853,7 +1877,7 @@ class GARModel:
             for name, on in (("sampling_warpers", sampling_warpers is not None), ("logits_processing", logits_processing is not None),
                              ("return_logprobs", return_logprobs), ("top_logprobs", top_logprobs),
                              ("candidate_token_ids", candidate_token_ids), ("forced_tokens", forced_tokens is not None),
-                             ("per-row requests", _row_words is not None)):
+                             ("per-row requests", _row_words is not None or _row_proc is not None)):
                 if on:
                     raise hip.GarError(f"beam_search with {name} is not implemented (DESIGN 7.11)")
             if self.kv_cache_dtype == "fp8":
@@ -1863,6 +1887,9 @@ class GARModel:
         warpers = None if warpers.neutral else warpers
         proc = LogitsProcessing.coerce(logits_processing)
         proc = None if proc.neutral else proc
+        if _row_proc is not None and (proc is not None or forced_tokens is not None):
+            raise hip.GarError("generate_begin: per-row processing blocks go with no logits_processing of the call's own and no "
+                               "forced_tokens")
         if proc is not None:
             if forced_tokens is not None:
                 raise hip.GarError("logits_processing with forced_tokens is not implemented (the processors read the history from the "
@@ -1911,6 +1938,8 @@ class GARModel:
                                              attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, validate,
                                              return_logits, sync_every, feature_replay_video, video_frame_tokens, state_slot)
         self._check_decode_rows(B * N, "generate")
+        if N > 1 and _row_proc is not None:
+            raise hip.GarError("generate_begin: per-row processing blocks with num_return_sequences > 1 are not implemented")
         if N > 1:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
@@ -1931,6 +1960,12 @@ class GARModel:
                 raise hip.GarError("generate_begin: one request of eight words per row, and no do_sample of the call's own")
             st["row_words"] = self._buf(skey, "row_words", (B, ops.SAMPLE_ROW_WORDS), torch.int32)
             st["row_words"].copy_(self._upload([w for r in _row_words for w in r], torch.int32, cache=False).view(B, -1))
+        if _row_proc is not None:       # ContinuousBatcher(processing=True): the rows' own blocks, their step 0 at column 0 of this state
+            if len(_row_proc) != B or any(not ops.LOGITS_PROCESS_HEADER <= len(r) <= ops.LOGITS_PROCESS_WORDS for r in _row_proc):
+                raise hip.GarError(f"generate_begin: one processing block of {ops.LOGITS_PROCESS_HEADER}.."
+                                   f"{ops.LOGITS_PROCESS_WORDS} words per row")
+            st["row_proc"] = self._buf(skey, "row_proc", (B, ops.LOGITS_PROCESS_WORDS), torch.int32)
+            st["row_proc"].copy_(_process_blocks(_row_proc))
         to = _PickTargets.of(st, out_tokens)
         V = cfg.mllm_config.text_config.vocab_size
         first_logits = []
@@ -2314,6 +2349,7 @@ class GARModel:
                 (st["tk"]["k"], st["tk"]["C"]) if st.get("tk") else (0, 0),  # top_logprobs / candidates: one more launch, planes by (k, C)
                 st.get("proc") is not None,                                 # logits_processing: one more launch in front of the pick
                 st.get("row_words") is not None,                            # per-row requests: the step picks with gar_sample_rows
+                st.get("row_proc") is not None,                             # per-row processing: gar_logits_process_rows in front of the pick
                 bool(st.get("warpers")),                                    # sampling_warpers: the step draws with gar_sample_ext
                 st["beam"]["key"] if st.get("beam") else None)              # beam_search: the step picks with gar_beam_step, buffers by (K, M, T)
         g = self._graphs.get(gkey)

@@ -759,23 +759,39 @@ def logits_process_max_vocab() -> int:
     return int(lib().gar_logits_process_max_vocab())
 
 
-def logits_process(logits, V, out_tokens, step_dev, eos_ids, params):
-    """``gar_logits_process``: HF's repetition penalty / no-repeat n-gram / min-new-tokens / suppress / begin-suppress / bad-words
-    processors on the rows of ``logits`` [B, ld] in place, before the pick. The history of row b is ``out_tokens[b, :step_dev[0]]``
-    (int64 [B, cols], row-strided view allowed; ``step_dev`` None = step 0, ``out_tokens`` None = no history); ``eos_ids`` int64 [n]
-    (entries < 0 never match); ``params`` int32 device block laid out by :meth:`LogitsProcessing.pack`."""
+def _logits_process_args(logits, V, out_tokens, step_dev, eos_ids):
+    """the arguments :func:`logits_process` and :func:`logits_process_rows` share, checked: everything in front of the block"""
     B = logits.shape[0]
     assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype in (torch.float32, torch.bfloat16, torch.float16)
-    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() >= LOGITS_PROCESS_HEADER
     assert eos_ids is None or (eos_ids.dtype == torch.int64 and eos_ids.is_contiguous())
     cols = stride = 0
     if out_tokens is not None:
         assert out_tokens.dtype == torch.int64 and out_tokens.dim() == 2 and out_tokens.shape[0] == B and \
             (out_tokens.shape[1] <= 1 or out_tokens.stride(1) == 1)
         cols, stride = out_tokens.shape[1], out_tokens.stride(0)
-    check(lib(logits.dtype).gar_logits_process(dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), stride,
-                                               cols, ptr(step_dev), ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(),
-                                               ptr(params), params.numel(), stream()), "gar_logits_process")
+    return (dtype_code(logits.dtype), ptr(logits), logits.stride(0), B, V, ptr(out_tokens), stride, cols, ptr(step_dev), ptr(eos_ids),
+            0 if eos_ids is None else eos_ids.numel())
+
+
+def logits_process(logits, V, out_tokens, step_dev, eos_ids, params):
+    """``gar_logits_process``: HF's repetition penalty / no-repeat n-gram / min-new-tokens / suppress / begin-suppress / bad-words
+    processors on the rows of ``logits`` [B, ld] in place, before the pick. The history of row b is ``out_tokens[b, :step_dev[0]]``
+    (int64 [B, cols], row-strided view allowed; ``step_dev`` None = step 0, ``out_tokens`` None = no history); ``eos_ids`` int64 [n]
+    (entries < 0 never match); ``params`` int32 device block laid out by :meth:`LogitsProcessing.pack`."""
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() >= LOGITS_PROCESS_HEADER
+    head = _logits_process_args(logits, V, out_tokens, step_dev, eos_ids)
+    check(lib(logits.dtype).gar_logits_process(*head, ptr(params), params.numel(), stream()), "gar_logits_process")
+
+
+def logits_process_rows(logits, V, out_tokens, step_dev, eos_ids, row_params):
+    """``gar_logits_process_rows``: :func:`logits_process` with a block per row — ``row_params`` int32 [B, LOGITS_PROCESS_WORDS]
+    (device, contiguous), row b laid out by :func:`continuous.pack_process_row`: :meth:`LogitsProcessing.pack`'s words with header
+    word 7 = ``col0``, the token column of the row's step 0. The row's step is ``step_dev[0] - col0`` and its history
+    ``out_tokens[b, col0:step_dev[0]]``; a row whose word 0 is 0 has no request and keeps its bytes."""
+    B = logits.shape[0]
+    assert row_params.dtype == torch.int32 and row_params.is_contiguous() and tuple(row_params.shape) == (B, LOGITS_PROCESS_WORDS)
+    head = _logits_process_args(logits, V, out_tokens, step_dev, eos_ids)
+    check(lib(logits.dtype).gar_logits_process_rows(*head, ptr(row_params), row_params.shape[1], stream()), "gar_logits_process_rows")
 
 
 def input_check(input_ids, vocab: int, counts, n_rows: int, spans, span_len: int, has_box, flags, attn_mask=None):

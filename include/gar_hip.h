@@ -563,6 +563,26 @@ int gar_logits_process(int dtype, void* logits, int64_t ld, int B, int V, const 
                        int params_words, gar_stream_t stream);
 int gar_logits_process_max_vocab(void);
 
+/* ---- Per-row logits processors in one batch (ContinuousBatcher(processing=True)) ------------------------------------------------------
+ * Additive: one entry point beside gar_logits_process, whose signature and results stand, so GAR_ABI_VERSION stays 16. The rows of one
+ * launch belong to different requests: row b is processed under its own parameter block row_params + b * row_words — device int32
+ * [B][row_words], read on every launch, so one captured graph serves any values. A block is laid out exactly as gar_logits_process's
+ * params_dev (header of 8 words, then the suppress ids, the begin-suppress ids, the bad-word offsets, the bad-word tokens) with one
+ * change: header word [7] is the row's col0, the column of the token matrix at which the row's step 0 was written.
+ * With c = step_dev[0] (NULL = 0) clamped to [0, out_cols] and col0 clamped to [0, c], the row's own step is t = c - col0 and its
+ * history out_tokens[b * out_stride + col0 .. c - 1]: columns in front of col0 (retired captions of the same row) are never read.
+ * A row whose header word [0] is 0 has no request — LogitsProcessing.pack() never produces that word, the f32 bits of a penalty > 0 —
+ * and its workgroup leaves after reading that one word: nothing of the row is read or written.
+ * Every other row gets what gar_logits_process writes on that row alone under its block with the history at columns 0 .. t - 1, bit
+ * for bit: one device function forms both kernels. Otherwise gar_logits_process's contract: ONE launch per step, one 1024-thread
+ * workgroup per row, V <= gar_logits_process_max_vocab(); every read of a block is bounded by row_words (a block whose lists do not
+ * fit names no list; row_words >= 8), every read of the history by out_cols, every marked id by V; each entry is computed from the
+ * value stored before the launch and written at most once, by one thread; no allocation, no synchronisation, hipGraph-capturable,
+ * deterministic. */
+int gar_logits_process_rows(int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens, int64_t out_stride,
+                            int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos,
+                            const int32_t* row_params /* device int32 [B][row_words] */, int row_words, gar_stream_t stream);
+
 /* ---- Per-row requests in one batch (ContinuousBatcher(sampling=True)) ----------------------------------------------------------------
  * Additive: one entry point beside gar_sample / gar_argmax, whose signatures and results stand, so GAR_ABI_VERSION stays 16. The rows
  * of one launch belong to different requests: row b picks its token under row_words[b] — device int32 [B][8], read on every launch,
