@@ -57,6 +57,10 @@ def base_parser(description):
                     help="HF's repetition penalty over the tokens generated so far (1.0 = off; e.g. 1.2 against a looping caption)")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0, metavar="N",
                     help="no N-gram of the generated tokens occurs twice (0 = off)")
+    ap.add_argument("--choices", default=None, metavar="A,B,...",
+                    help="comma-separated phrases: the answer is constrained to one of them (a token trie walked on the device, "
+                         "one mask launch per step) and printed as that phrase; with --return_logprobs behind its probability "
+                         "among the choices. Not combined with --num_beams")
     ap.add_argument("--synthetic_weights", action="store_true",
                     help="seeded random weights of the named size + the stub tokenizer (plumbing / benchmarking)")
     return ap
@@ -149,3 +153,20 @@ def top_logprob_lines(out, row, tokenizer):
             break
         lines.append("    " + "  ".join(f"{tokenizer.decode([i])!r}:{p:.4f}" for i, p in zip(ids, lps)))
     return lines
+
+
+def constraint_kwargs(args, processor):
+    """generate() keywords of --choices: the constraint parameter over the comma-separated phrases"""
+    if not getattr(args, "choices", None):
+        return {}
+    from gar_amd import PhraseConstraint
+    texts = [c.strip() for c in args.choices.split(",") if c.strip()]
+    return dict(constraint=PhraseConstraint.from_text(processor.tokenizer, texts))
+
+
+def print_choices(out, constraint, return_logprobs=False):
+    """--choices: one line per row — the phrase the row completed (or a note that max_new_tokens cut it); with log-probabilities
+    behind its probability, exp(sum_logprobs): the phrase's probability renormalised over the allowed set at every step"""
+    for r, i in enumerate(out.phrase_index.tolist()):
+        text = constraint.text_of(0, i) if i >= 0 else "(no choice completed within max_new_tokens)"
+        print(f"[{float(out.sum_logprobs[r].exp()):.4f}] {text}" if return_logprobs else text)

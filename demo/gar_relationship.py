@@ -4,8 +4,8 @@
 import numpy as np
 from PIL import Image
 
-from _common import (base_parser, beam_search_kwargs, generation_config, load, logits_processing_kwargs, print_hypotheses,
-                     sampling_kwargs, top_logprob_lines)
+from _common import (base_parser, beam_search_kwargs, constraint_kwargs, generation_config, load, logits_processing_kwargs,
+                     print_choices, print_hypotheses, sampling_kwargs, top_logprob_lines)
 
 
 def main():
@@ -13,6 +13,8 @@ def main():
     ap.add_argument("--image_path", required=True)
     ap.add_argument("--mask_paths", nargs="+", required=True)
     ap.add_argument("--question_str", required=True)
+    ap.add_argument("--return_logprobs", action="store_true",
+                    help="with --choices: print the chosen phrase's probability among the choices in front of it")
     args = ap.parse_args()
     model, processor, dtype = load(args)
     from evaluation.eval_dataset import MultiRegionDataset
@@ -26,8 +28,13 @@ def main():
                                  device=args.device)
     data_sample = dataset[0]
     gc = generation_config(args, processor)
+    choices = constraint_kwargs(args, processor)
     out = model.generate(**data_sample, generation_config=gc, return_dict=True, top_logprobs=args.top_logprobs,
-                         **sampling_kwargs(args, gc), **logits_processing_kwargs(args), **beam_search_kwargs(args))
+                         return_logprobs=bool(choices) and args.return_logprobs, **sampling_kwargs(args, gc),
+                         **logits_processing_kwargs(args), **beam_search_kwargs(args), **choices)
+    if choices:                             # --choices: the phrase each row completed
+        print_choices(out, choices["constraint"], args.return_logprobs)
+        return
     if out.sequences_scores is not None:    # --num_beams: the hypotheses, best first
         print_hypotheses(out, processor.tokenizer)
         return

@@ -4,8 +4,8 @@ demo/gar_with_mask.py (same flags: --model_name_or_path --image_path --mask_path
 import numpy as np
 from PIL import Image
 
-from _common import (base_parser, beam_search_kwargs, generation_config, load, logits_processing_kwargs, print_hypotheses,
-                     sampling_kwargs, top_logprob_lines)
+from _common import (base_parser, beam_search_kwargs, constraint_kwargs, generation_config, load, logits_processing_kwargs,
+                     print_choices, print_hypotheses, sampling_kwargs, top_logprob_lines)
 
 
 def main():
@@ -26,9 +26,13 @@ def main():
                                          visual_prompt_tokens=prompt_tokens, data_dtype=dtype, device=args.device)
     data_sample = dataset[0]
     gc = generation_config(args, processor)
+    choices = constraint_kwargs(args, processor)
     out = model.generate(**data_sample, generation_config=gc, return_dict=True, return_logprobs=args.return_logprobs,
                          top_logprobs=args.top_logprobs, **sampling_kwargs(args, gc), **logits_processing_kwargs(args),
-                         **beam_search_kwargs(args))
+                         **beam_search_kwargs(args), **choices)
+    if choices:                             # --choices: the phrase each row completed
+        print_choices(out, choices["constraint"], args.return_logprobs)
+        return
     if out.sequences_scores is not None:    # --num_beams: the hypotheses, best first
         print_hypotheses(out, processor.tokenizer)
         return

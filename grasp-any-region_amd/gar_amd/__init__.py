@@ -6,7 +6,9 @@ PyTorch fallback: importing :mod:`gar_amd.hip` without the built library raises.
 """
 from .configuration_gar import GARConfig, PerceptionLMConfig, TextConfig, VisionConfig  # noqa: F401
 from .beam_search import BeamSearch  # noqa: F401
+from .constrained import PhraseConstraint  # noqa: F401
 from .logits_processing import LogitsProcessing  # noqa: F401
 from .sampling_warpers import SamplingWarpers  # noqa: F401
 
-__all__ = ["GARConfig", "PerceptionLMConfig", "TextConfig", "VisionConfig", "LogitsProcessing", "SamplingWarpers", "BeamSearch"]
+__all__ = ["GARConfig", "PerceptionLMConfig", "TextConfig", "VisionConfig", "LogitsProcessing", "SamplingWarpers", "BeamSearch",
+           "PhraseConstraint"]

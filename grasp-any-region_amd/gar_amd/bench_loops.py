@@ -104,6 +104,7 @@ def write_run_meta(path, args, model):
             **({"do_sample": True, "seed": args.seed, "temperature": args.temperature, "top_k": args.top_k, "top_p": args.top_p}
                if getattr(args, "do_sample", False) else {}),
             **({"logits_processing": processing_options(args)} if processing_options(args) else {}),
+            **({"constrain_options": True} if getattr(args, "constrain_options", False) else {}),
             "data_type": args.data_type,
             "max_num_tiles": args.max_num_tiles, "max_new_tokens": args.max_new_tokens,
             "synthetic_weights": bool(args.synthetic_weights), "host_preprocessing": bool(args.host_preprocessing),
@@ -124,14 +125,18 @@ def hip_abi_version():
     return hip.ABI_VERSION
 
 
-def _generate(model, processor, sample, args, skip_special_tokens, candidate_token_ids=None):
+def _generate(model, processor, sample, args, skip_special_tokens, candidate_token_ids=None, phrases=None):
     """the decoded answer of one item; with ``candidate_token_ids`` (--option_logprobs) also the first step's log-probabilities
-    of those ids"""
+    of those ids; with ``phrases`` (--constrain_options) the answer is one of them and its index comes with it"""
     extra = {} if candidate_token_ids is None else dict(candidate_token_ids=candidate_token_ids)
+    if phrases is not None:
+        extra["constraint"] = dict(phrases=phrases)
     out = model.generate(**sample, generation_config=dict(
         max_new_tokens=args.max_new_tokens, do_sample=False, eos_token_id=processor.tokenizer.eos_token_id,
         pad_token_id=processor.tokenizer.pad_token_id), return_dict=True, **extra)
     text = processor.tokenizer.decode(out.sequences[0], skip_special_tokens=skip_special_tokens).strip()
+    if phrases is not None:
+        return text, int(out.phrase_index[0])
     return text if candidate_token_ids is None else (text, out.candidate_logprobs[0, 0].tolist())
 
 
@@ -143,7 +148,9 @@ class Batcher:
     stream is shared by the whole batch instead of being paid per item. A row's text is cut at its own first EOS, which is
     what a one-item call returns. ``generate_calls`` / ``items`` count what was run (tests). An item added with
     ``candidate_token_ids`` (--option_logprobs) is batched with items of the same id list — one list per ``generate`` — and its
-    ``finish`` also gets the first step's log-probabilities of those ids."""
+    ``finish`` also gets the first step's log-probabilities of those ids. An item added with ``phrases`` (--constrain_options) is
+    answered with one of them: items with different phrase sets share one ``generate`` (per-prompt sets), and ``finish`` also
+    gets the index of the phrase the answer is (-1: ``max_new_tokens`` cut it)."""
 
     def __init__(self, model, processor, args, skip_special_tokens):
         self.model, self.processor, self.args, self.skip = model, processor, args, skip_special_tokens
@@ -153,10 +160,10 @@ class Batcher:
         self.generate_calls = 0
         self.items = 0
 
-    def add(self, idx, sample, finish, candidate_token_ids=None):
+    def add(self, idx, sample, finish, candidate_token_ids=None, phrases=None):
         if self.bs == 1:
-            got = _generate(self.model, self.processor, sample, self.args, self.skip, candidate_token_ids)
-            self._emit(idx, got, finish) if candidate_token_ids is None else self._emit(idx, got[0], finish, got[1])
+            got = _generate(self.model, self.processor, sample, self.args, self.skip, candidate_token_ids, phrases)
+            self._emit(idx, got, finish) if candidate_token_ids is None and phrases is None else self._emit(idx, got[0], finish, got[1])
             self.generate_calls += 1
             self.items += 1
             return
@@ -164,6 +171,9 @@ class Batcher:
                bool(sample.get("feature_replay_video")))
         if candidate_token_ids is not None:
             key += (tuple(candidate_token_ids),)
+        elif phrases is not None:
+            key += ("phrases",)     # one group whatever the sets: each row carries its own
+            sample = dict(sample, _phrases=phrases)
         g = self.groups.setdefault(key, [])
         g.append((idx, sample, finish))
         if len(g) >= self.bs:
@@ -171,7 +181,7 @@ class Batcher:
 
     def flush(self):
         for key in list(self.groups):      # a key with a 4th entry carries its group's candidate id list
-            self._run(self.groups.pop(key), list(key[3]) if len(key) > 3 else None)
+            self._run(self.groups.pop(key), list(key[3]) if len(key) > 3 and key[3] != "phrases" else None)
         print(f"[batcher] {self.items} items in {self.generate_calls} generate calls (batch_size {self.bs})", flush=True)
         return self.results
 
@@ -185,6 +195,7 @@ class Batcher:
         eos_set = set(eos) if isinstance(eos, (list, tuple)) else {eos}
         pad = tk.pad_token_id if tk.pad_token_id is not None else next(iter(eos_set))
         samples = [s for _, s, _ in group]
+        phrases = [s["_phrases"] for s in samples] if "_phrases" in samples[0] else None
         S = max(int(s["input_ids"].shape[1]) for s in samples)
         dev = samples[0]["input_ids"].device
         ids = torch.full((len(samples), S), int(pad), dtype=torch.int64, device=dev)
@@ -203,11 +214,14 @@ class Batcher:
             batch.update(feature_replay_video=True, video_frame_tokens=samples[0]["video_frame_tokens"])
         out = self.model.generate(**batch, generation_config=dict(
             max_new_tokens=self.args.max_new_tokens, do_sample=False, eos_token_id=eos, pad_token_id=pad), return_dict=True,
-            **({} if candidate_token_ids is None else dict(candidate_token_ids=candidate_token_ids)))
+            **({} if candidate_token_ids is None else dict(candidate_token_ids=candidate_token_ids)),
+            **({} if phrases is None else dict(constraint=dict(phrases=phrases))))
         self.generate_calls += 1
         self.items += len(samples)
         rows = out.sequences.tolist()
         first = None if candidate_token_ids is None else out.candidate_logprobs[:, 0].tolist()
+        if phrases is not None:
+            first = out.phrase_index.tolist()
         for r, ((idx, _, finish), row) in enumerate(zip(group, rows)):
             cut = next((j + 1 for j, t in enumerate(row) if t in eos_set), len(row))     # its own EOS, inclusive
             self._emit(idx, tk.decode(row[:cut], skip_special_tokens=self.skip).strip(), finish, *([] if first is None else [first[r]]))
@@ -319,6 +333,11 @@ def option_token_ids(tokenizer, letters):
     return ids
 
 
+def option_phrases(tokenizer, letters):
+    """the token ids of every option letter (encoded without special tokens), however many tokens a letter takes"""
+    return [[int(i) for i in tokenizer([letter], add_special_tokens=False)["input_ids"][0]] for letter in letters]
+
+
 def gar_bench_parser():
     ap = base_parser("Inference of Grasp Any Region models on GAR-Bench (MI355X-native path).", "HaochenWang/GAR-8B",
                      "gar_8b", "evaluation/GAR-Bench/annotations")
@@ -327,6 +346,10 @@ def gar_bench_parser():
                     help="--mode vqa: each record also gets option_logprobs — the log-probability of every option's letter as the "
                          "FIRST generated token, in `choices` order (generate(candidate_token_ids=...)) — and option_pick, the letter "
                          "of the largest; model_output and the accuracy print-out are unchanged. Not with --continuous")
+    ap.add_argument("--constrain_options", action="store_true",
+                    help="--mode vqa: every item's answer is constrained to its own option letters (generate(constraint=...), a "
+                         "letter may take several tokens; items with different options share a batch) and each record gets "
+                         "option_pick, the letter the answer is. Not with --continuous, not with --option_logprobs")
     return ap
 
 
@@ -337,6 +360,12 @@ def run_gar_bench(argv=None):
         raise SystemExit("--option_logprobs goes with --mode vqa (the items' `choices` name the option letters)")
     if args.option_logprobs and args.continuous:
         raise SystemExit("--option_logprobs is not implemented with --continuous (ContinuousBatcher returns token lists only)")
+    if args.constrain_options and args.mode != "vqa":
+        raise SystemExit("--constrain_options goes with --mode vqa (the items' `choices` name the option letters)")
+    if args.constrain_options and args.continuous:
+        raise SystemExit("--constrain_options is not implemented with --continuous (a ticket carries no constraint, DESIGN 7.13)")
+    if args.constrain_options and args.option_logprobs:
+        raise SystemExit("--constrain_options and --option_logprobs do not combine (one group key per item)")
     model, processor, dtype, device, rank, world = load(args)
     data = json.load(open(args.anno_file))
     if args.limit:
@@ -351,6 +380,8 @@ def run_gar_bench(argv=None):
                 text = text.replace("<|eot_id|>", "")
             if option_logprobs is None:
                 return dict(item, model_output=text)
+            if isinstance(option_logprobs, int):        # --constrain_options: the index of the letter the answer is (-1: cut)
+                return dict(item, model_output=text, option_pick=letters[option_logprobs] if option_logprobs >= 0 else None)
             pick = letters[max(range(len(letters)), key=lambda c: option_logprobs[c])]
             return dict(item, model_output=text, option_logprobs=option_logprobs, option_pick=pick)
         return finish
@@ -364,6 +395,9 @@ def run_gar_bench(argv=None):
         if args.option_logprobs:
             letters = option_letters(item)
             runner.add(idx, ds[0], record(item, letters), candidate_token_ids=option_token_ids(processor.tokenizer, letters))
+        elif args.constrain_options:
+            letters = option_letters(item)
+            runner.add(idx, ds[0], record(item, letters), phrases=option_phrases(processor.tokenizer, letters))
         else:
             runner.add(idx, ds[0], record(item))
     outputs = _gather(runner.flush(), rank, world)

@@ -195,7 +195,7 @@ class ContinuousBatcher:
 
     # ---- queue ------------------------------------------------------------------------------------------------------
     def submit(self, sample: dict, generation_config=None, seed: Optional[int] = None, sampling_warpers=None,
-               beam_search=None, logits_processing=None, **generate_kwargs) -> int:
+               beam_search=None, logits_processing=None, constraint=None, **generate_kwargs) -> int:
         """queue one region. The generation options are read as ``generate`` reads them (a GenerationConfig / dict with the
         keyword arguments laid over it; HF's defaults, so ``top_k`` 50): ``do_sample=True`` — on a batcher built with
         ``sampling=True`` — makes this ticket a sampled one under its own temperature / top_k / top_p and ``seed`` (None: drawn
@@ -217,6 +217,10 @@ class ContinuousBatcher:
             raise hip.GarError("ContinuousBatcher.submit: return_logprobs is not implemented (call generate(return_logprobs=True))")
         if beam_search is not None or sample.get("beam_search") is not None:
             raise hip.GarError("ContinuousBatcher.submit: beam_search is not implemented (call generate(beam_search=...))")
+        if constraint is not None or sample.get("constraint") is not None:
+            # a ticket's trie and node plane would have to move with its row (_rebase): per-ticket constraints are a follow-up
+            raise hip.GarError("constraint with ContinuousBatcher.submit is not implemented (DESIGN 7.13): call "
+                               "generate(constraint=...)")
         proc = self._read_processing(logits_processing)      # (in front of the options: a refused request draws no seed)
         request = self._read_options(generation_config, generate_kwargs, seed)
         t = self._next_ticket

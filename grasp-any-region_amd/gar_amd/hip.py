@@ -108,6 +108,7 @@ SIGNATURES = {
     "gar_logits_process": ([_i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _vp], _i),
     "gar_logits_process_max_vocab": ([], _i),
     "gar_logits_process_rows": ([_i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _vp], _i),
+    "gar_constrain": ([_i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _vp, _i64, _vp], _i),
     "gar_counter_add": ([_vp, _i, _i, _vp], _i),
     "gar_input_check": ([_vp, _i, _i, _i64, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
     "gar_gather_rmsnorm": ([_i, _vp, _i64, _i, _vp, _i, _vp, _vp, _i, _f, _vp], _i),

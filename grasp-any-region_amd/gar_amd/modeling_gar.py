@@ -22,6 +22,7 @@ import torch
 
 from . import hip, ops
 from .beam_search import BeamBudgetError, BeamSearch
+from .constrained import PhraseConstraint
 from .configuration_gar import GARConfig
 from .logits_processing import LogitsProcessing, _Refused as _ProcessingRefused
 from .sampling_warpers import SamplingWarpers
@@ -69,6 +70,9 @@ class GenerateOutput:
     # beam_search=BeamSearch(...) only: ``sequences`` is [B * num_return_sequences, n], each prompt's hypotheses best
     # first, ``pad`` behind each one's end; this is each one's sum of log-probabilities / length ** length_penalty
     sequences_scores: Optional[torch.Tensor] = None         # f32 [B * num_return_sequences]
+    # constraint=PhraseConstraint(...) only: the index, in the row's prompt's list, of the phrase the row completed —
+    # its tokens before its first eos, or all of them when max_new_tokens cut it, are exactly one phrase — else -1 (host tensor)
+    phrase_index: Optional[torch.Tensor] = None             # int32 [B * N]
 
 
 class _PickTargets(NamedTuple):
@@ -76,7 +80,8 @@ class _PickTargets(NamedTuple):
     its first row (the Philox row counter of a draw), the (raw, warped) log-probability planes of a return_logprobs request or
     None, the planes of a top_logprobs / candidate_token_ids request (GARModel._topk_planes) or None, the rows' own request
     words (int32 [rows, 8], gar_sample_rows) of a state that carries them or None, and the rows' own processing blocks (int32
-    [rows, LOGITS_PROCESS_WORDS], gar_logits_process_rows) of a state that carries them or None."""
+    [rows, LOGITS_PROCESS_WORDS], gar_logits_process_rows) of a state that carries them or None, and the rows of the node plane
+    (int32 [rows, cols + 1], gar_constrain) of a request with a phrase constraint or None."""
     out_tokens: torch.Tensor
     cur: torch.Tensor
     finished: torch.Tensor
@@ -85,10 +90,12 @@ class _PickTargets(NamedTuple):
     tk: Optional[dict]
     row_words: Optional[torch.Tensor] = None
     row_proc: Optional[torch.Tensor] = None
+    nodes: Optional[torch.Tensor] = None
 
     @classmethod
     def of(cls, st, out_tokens) -> "_PickTargets":          # every row of a state
-        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"), st.get("row_words"), st.get("row_proc"))
+        return cls(out_tokens, st["cur"], st["finished"], 0, st.get("lp"), st.get("tk"), st.get("row_words"), st.get("row_proc"),
+                   st.get("nodes"))
 
     def rows(self, r0: int, r1: int) -> "_PickTargets":
         """cut to rows r0 .. r1 - 1: a prompt chunk's first-token head"""
@@ -96,7 +103,8 @@ class _PickTargets(NamedTuple):
         return _PickTargets(self.out_tokens[r0:r1], self.cur[r0:r1], self.finished[r0:r1], self.row0 + r0,
                             self.lp and tuple(p[r0:r1] for p in self.lp), tk,
                             None if self.row_words is None else self.row_words[r0:r1],
-                            None if self.row_proc is None else self.row_proc[r0:r1])
+                            None if self.row_proc is None else self.row_proc[r0:r1],
+                            None if self.nodes is None else self.nodes[r0:r1])
 
 
 def _process_blocks(rows) -> torch.Tensor:
@@ -152,6 +160,11 @@ def top_logprob_outputs(tk, n: int, finished_at: Sequence[Optional[int]]):
 
 INPUT_COUNT_MISMATCH, INPUT_SPAN_LENGTH, INPUT_MISSING_BBOX, INPUT_ID_RANGE, INPUT_MASK_NOT_LEFT_PADDED = 1, 2, 4, 8, 16
 INPUT_LABEL_RANGE = 32          # score(validate=False): a label outside [0, vocab) and not -100 (set by gar_xent_combine)
+
+
+def phrase_indices(constraint: PhraseConstraint, rows, eos, fanout: int = 1) -> torch.Tensor:
+    """GenerateOutput.phrase_index of a constrained request from its ``sequences`` (as lists): row r belongs to prompt r // fanout"""
+    return torch.tensor([constraint.phrase_index(r // fanout, row, eos) for r, row in enumerate(rows)], dtype=torch.int32)
 
 
 def describe_input_flags(flags: int) -> str:
@@ -484,6 +497,8 @@ class GenerationPipeline:
     def __init__(self, model: "GARModel", **generate_kwargs):
         if generate_kwargs.get("beam_search") is not None:
             raise hip.GarError("GenerationPipeline / generate_pipelined: beam_search is not implemented (call generate)")
+        if generate_kwargs.get("constraint") is not None:
+            raise hip.GarError("constraint with GenerationPipeline / generate_pipelined is not implemented (DESIGN 7.13): call generate")
         self.model, self.kwargs = model, generate_kwargs
         self.side = None
         self.done = {}              # slot -> event: that slot's previous decode loop has finished
@@ -515,6 +530,8 @@ class GenerationPipeline:
             self.prev = None
         if sample.get("beam_search") is not None:
             raise hip.GarError("GenerationPipeline / generate_pipelined: beam_search is not implemented (call generate)")
+        if sample.get("constraint") is not None:
+            raise hip.GarError("constraint with GenerationPipeline / generate_pipelined is not implemented (DESIGN 7.13): call generate")
         slot = self.n & 1
         self.n += 1
         with torch.cuda.device(m.device):
@@ -1442,6 +1459,39 @@ class GARModel:
         buf[:len(words)].copy_(self._upload(words, torch.int32))
         st["proc"] = buf
 
+    def _arm_constraint(self, skey, st, constraint: Optional[PhraseConstraint], B: int, N: int, cols: int):
+        """st["trie"] / st["nodes"] of a request: None without a constraint, else the state's trie block with the request's phrases
+        uploaded and the node plane [B * N, cols + 1] with column 0 = every row's root — buffers of the state, so the captured step
+        that reads them serves any phrase set"""
+        st["trie"] = st["nodes"] = None
+        if constraint is None:
+            return
+        V = self.config.mllm_config.text_config.vocab_size
+        if V > ops.logits_process_max_vocab():
+            raise hip.GarError(f"constraint: vocab_size {V} above gar_constrain's {ops.logits_process_max_vocab()}")
+        try:
+            words = constraint.pack(V, B, N)
+        except _ProcessingRefused as e:
+            raise hip.GarError(str(e)) from None
+        trie = self._buf(skey, "trie", (ops.CONSTRAINT_WORDS,), torch.int32, zero=True)
+        host = torch.tensor(words, dtype=torch.int32)
+        trie[:len(words)].copy_(host)
+        nodes = self._buf(skey, "nodes", (B * N, cols + 1), torch.int32, zero=True)
+        nodes[:, 0].copy_(host[ops.CONSTRAINT_HEADER:ops.CONSTRAINT_HEADER + B * N])
+        st["trie"], st["nodes"] = trie, nodes
+
+    def _constrain(self, logits, V, st, out_tokens, nodes):
+        """the request's phrase constraint on ``logits`` in place (one gar_constrain launch) over the rows ``nodes`` of the node
+        plane; nothing — no launch — for a request without one. ``out_tokens`` None: step 0, no history."""
+        if nodes is None:
+            return
+        step = None
+        if out_tokens is not None:      # as _process: the history's bound is the token buffer's row, not the slice's width
+            cap = out_tokens.stride(0)
+            out_tokens = out_tokens.as_strided((out_tokens.shape[0], cap), (cap, 1), out_tokens.storage_offset())
+            step = st["counters"][2:3]
+        ops.constrain(logits, V, out_tokens, step, st["eos_ids"], st["trie"], nodes)
+
     def _pick(self, logits, V, st, to: "_PickTargets", process: bool = True):
         """the token of every row of ``logits`` into ``to``, by the request words of ``st``: the request's logits processors first
         (gar_logits_process, in place; ``process`` False: the caller ran them), then one gar_topk_lp when the request
@@ -1460,6 +1510,7 @@ class GARModel:
             raise hip.GarError("per-row processing blocks carry no log-probability planes (they are defined over the unprocessed logits)")
         if process:
             self._process(logits, V, st, to.out_tokens, to.row_proc)
+            self._constrain(logits, V, st, to.out_tokens, to.nodes)      # behind the processors: HF's order, and -inf stays -inf
         if tk is not None:
             ws = self._buf(key, f"tkws{tk['k']}", (ops.topk_lp_workspace(B, V, tk["k"]),), torch.uint8)   # by k: a captured step keeps its own
             ops.topk_lp(logits, V, step, ws, top_ids=tk["ids"], top_lp=tk["lp"], cand_ids=tk["cand_ids"], cand_lp=tk["cand_lp"])
@@ -1548,7 +1599,7 @@ class GARModel:
             _, pst = self._llm_state(B, Smax, state_slot)
             skey, st = self._llm_state(R, Smax, state_slot)
         out_tokens = self._buf(skey, "out_tokens", (R, T if shared else Smax), torch.int64, zero=True)[:, :max_new_tokens]
-        st["lp"] = st["tk"] = st["proc"] = None
+        st["lp"] = st["tk"] = st["proc"] = st["trie"] = st["nodes"] = None
         self._arm_state(pst, left_pad, None, None, None)
         eos_list, _ = self._arm_state(st, None, eos_token_id, None, None)
         bs = self._beam_state(skey, st, B, K, M, T, beam, max_new_tokens, eos_list)
@@ -1821,7 +1872,7 @@ class GARModel:
                        video_frame_tokens: Optional[Sequence[int]] = None, forced_tokens: Optional[torch.Tensor] = None,
                        state_slot: int = 0, seed: Optional[int] = None, return_logprobs: bool = False,
                        top_logprobs: int = 0, candidate_token_ids: Optional[Sequence[int]] = None, logits_processing=None,
-                       sampling_warpers=None, beam_search=None, _row_words=None, _row_proc=None,
+                       sampling_warpers=None, beam_search=None, constraint=None, _row_words=None, _row_proc=None,
                        **generate_kwargs) -> "_PendingGeneration":
         """Region captioning, reference semantics of GARModel.generate (modeling_gar.py:295-428): greedy search, or — with
         ``do_sample=True`` in the generation config — temperature / top-k / top-p sampling on the device (``seed``: the Philox key of
@@ -1871,7 +1922,25 @@ class GARModel:
         ``do_sample``, ``sampling_warpers``, ``logits_processing`` (HF processes the log-probabilities behind the softmax with each
         beam's own history: a follow-up), ``return_logprobs`` / ``top_logprobs`` / ``candidate_token_ids``, ``forced_tokens`` and
         ``kv_cache_dtype="fp8"``, and ``num_beams * max(2, 1 + number of eos ids) > 32``. The GenerationConfig fields
-        ``num_beams`` / ``length_penalty`` stay refused."""
+        ``num_beams`` / ``length_penalty`` stay refused.
+
+        ``constraint``: a :class:`PhraseConstraint` (or a dict with ``phrases``) — the answer is taken from a closed set of token
+        phrases, shared by the prompts or one set per prompt: HF's ``PrefixConstrainedLogitsProcessor`` under the
+        callback "the generated tokens stay a prefix of one of the prompt's phrases", as one launch per step that walks a token
+        trie on the device and masks the logits, behind ``logits_processing`` and in front of the pick. Needs ``eos_token_id`` (at
+        most ``MAX_EOS_IDS`` ids): eos is allowed once a phrase is complete, and alone behind it. ``phrase_index`` reports the
+        phrase every row completed. ``return_logits=True`` returns the masked scores (HF's ``scores``); ``return_logprobs`` /
+        ``top_logprobs`` / ``candidate_token_ids`` are taken over the masked scores too, so ``sum_logprobs`` is the chosen
+        phrase's log-probability renormalised over the allowed set at every step. Composes with ``do_sample``,
+        ``sampling_warpers``, ``num_return_sequences`` and ``logits_processing``. None: the path, the launches and the captured
+        graph of a call without it. Refused with ``GarError``: together with ``beam_search``, ``forced_tokens`` and per-row
+        requests (``ContinuousBatcher``), and in ``GenerationPipeline`` / ``generate_pipelined``."""
+        constraint = PhraseConstraint.coerce(constraint)
+        if constraint is not None:
+            for name, on in (("beam_search", beam_search is not None), ("forced_tokens", forced_tokens is not None),
+                             ("ContinuousBatcher.submit", _row_words is not None or _row_proc is not None)):
+                if on:
+                    raise hip.GarError(f"constraint with {name} is not implemented (DESIGN 7.13)")
         beam = BeamSearch.coerce(beam_search)
         if beam is not None:
             for name, on in (("sampling_warpers", sampling_warpers is not None), ("logits_processing", logits_processing is not None),
@@ -1924,6 +1993,13 @@ class GARModel:
         max_new_tokens = int(max_new_tokens or 64)
         cfg = self.config
         B, S = input_ids.shape
+        if constraint is not None:
+            n_eos = 0 if eos_token_id is None else (len(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else 1)
+            if not 1 <= n_eos <= GARModel.MAX_EOS_IDS:
+                raise hip.GarError(f"constraint needs eos_token_id with 1..{GARModel.MAX_EOS_IDS} ids on the device, got {n_eos}: a complete "
+                                   "phrase could never end otherwise")
+            if constraint.per_prompt and len(constraint.sets) != B:
+                raise ValueError(f"constraint: {len(constraint.sets)} per-prompt phrase sets for a batch of {B} prompts")
         if beam is not None:
             n_eos = 0 if eos_token_id is None else (len(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else 1)
             try:            # HF's beams_to_keep: known only now that the eos ids are
@@ -1944,7 +2020,7 @@ class GARModel:
             return self._generate_begin_fanout(N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate,
                                                return_logits, sync_every, feature_replay_video, video_frame_tokens, forced_tokens,
-                                               state_slot, return_logprobs, top_k_lp, cands, proc, warpers)
+                                               state_slot, return_logprobs, top_k_lp, cands, proc, warpers, constraint)
         left_pad, forced_tokens = self._begin_inputs(input_ids, attention_mask, validate, forced_tokens)
         # KV capacity in buckets of 256 positions: evaluation loops with a different prompt length per item reuse one
         # cache, one token buffer ([B, Smax], sliced) and one captured decode graph per bucket
@@ -1955,6 +2031,7 @@ class GARModel:
         self._topk_planes(skey, st, (B, Smax), top_k_lp, cands)
         eos_list, eos_on_device = self._arm_state(st, left_pad, eos_token_id, sampling, seed, warpers)
         self._arm_processing(skey, st, proc, eos_list, eos_on_device)
+        self._arm_constraint(skey, st, constraint, B, 1, Smax)
         if _row_words is not None:      # ContinuousBatcher(sampling=True): the rows of this prompt phase pick under requests of their own
             if len(_row_words) != B or sampling is not None:
                 raise hip.GarError("generate_begin: one request of eight words per row, and no do_sample of the call's own")
@@ -1987,7 +2064,7 @@ class GARModel:
         return self._begin_pending(first_logits, eos_list, eos_on_device=eos_on_device, st=st, skey=skey, B=B, Smax=Smax,
                                    out_tokens=out_tokens, max_new_tokens=max_new_tokens, pad_token_id=pad_token_id,
                                    return_logits=return_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
-                                   sync_every=sync_every, N=1)
+                                   sync_every=sync_every, N=1, constraint=constraint)
 
     def _begin_inputs(self, input_ids, attention_mask, validate: bool, forced_tokens):
         """What both begin methods do with a request's inputs before they touch a state: the mask's left padding, forced_tokens
@@ -2053,7 +2130,7 @@ class GARModel:
     def _generate_begin_fanout(self, N, pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, attention_mask,
                                max_new_tokens, eos_token_id, pad_token_id, sampling, seed, use_graph, validate, return_logits,
                                sync_every, feature_replay_video, video_frame_tokens, forced_tokens, state_slot,
-                               return_logprobs=False, top_k_lp=0, cands=(), proc=None, warpers=None):
+                               return_logprobs=False, top_k_lp=0, cands=(), proc=None, warpers=None, constraint=None):
         """generate_begin of a num_return_sequences = N > 1 request (do_sample): ONE prompt phase over the B prompts, N first
         tokens drawn from each prompt's logits, and a state of B * N rows for :meth:`generate_finish` — row b * N + i is sample i
         of prompt b, its draws counted by (seed, step, b * N + i) as the replicated batch's would be.
@@ -2083,6 +2160,7 @@ class GARModel:
         self._arm_state(pst, left_pad, None, None, None)
         eos_list, eos_on_device = self._arm_state(st, None, eos_token_id, sampling, seed, warpers)
         self._arm_processing(skey, st, proc, eos_list, eos_on_device)
+        self._arm_constraint(skey, st, constraint, B, N, Smax - Sp if shared else Smax)
         to = _PickTargets.of(st, out_tokens)
         first_logits = []
         for b0, b1, embeds in self._prompt_chunks(pixel_values, global_mask_values, aspect_ratios, bboxes, input_ids, validate,
@@ -2092,6 +2170,7 @@ class GARModel:
             r0, r1 = _fanout_rows(b0, b1, N)
             # the history of every row is empty at step 0: the N draws of a prompt share ONE processed row
             self._process(lg, V, st, None)
+            self._constrain(lg, V, st, None, None if to.nodes is None else to.nodes[r0:r1:N])      # the N rows share the prompt's root
             lg = lg.repeat_interleave(N, 0)                                        # the SAME logits for the N draws
             self._pick(lg, V, st, to.rows(r0, r1), process=False)   # the N rows of a prompt carry that prompt's top-k / candidate values at step 0
             if forced_tokens is not None:
@@ -2113,7 +2192,7 @@ class GARModel:
         return self._begin_pending(first_logits, eos_list, eos_on_device=eos_on_device, st=st, skey=skey, B=R, Smax=Smax,
                                    out_tokens=out_tokens, max_new_tokens=max_new_tokens, pad_token_id=pad_token_id,
                                    return_logits=return_logits, forced_tokens=forced_tokens, use_graph=use_graph, validate=validate,
-                                   sync_every=sync_every, N=N)
+                                   sync_every=sync_every, N=N, constraint=constraint)
 
     # ---- teacher-forced scoring ---------------------------------------------------------------------------------------
     XENT_CHUNK_ROWS = 8192          # scored rows per fused-head launch: partials workspace <= chunk x 16 KiB at V = 128256
@@ -2308,6 +2387,9 @@ class GARModel:
             lp_fields = dict(zip(names, logprob_outputs(raw, warped, finished_at if eos else [None] * B)))
         if st.get("tk") is not None:
             lp_fields.update(top_logprob_outputs(st["tk"], seq.shape[1], finished_at if eos else [None] * B))
+        constraint = getattr(pend, "constraint", None)
+        if constraint is not None:
+            lp_fields["phrase_index"] = phrase_indices(constraint, seq.tolist(), eos, pend.N)
         return GenerateOutput(sequences=seq, logits=torch.stack(all_logits, 1) if return_logits else None,
                               input_flags=None if validate else self._input_flags, **lp_fields)
 
@@ -2351,6 +2433,7 @@ class GARModel:
                 st.get("row_words") is not None,                            # per-row requests: the step picks with gar_sample_rows
                 st.get("row_proc") is not None,                             # per-row processing: gar_logits_process_rows in front of the pick
                 bool(st.get("warpers")),                                    # sampling_warpers: the step draws with gar_sample_ext
+                st.get("nodes") is not None,                                # constraint: one more launch in front of the pick
                 st["beam"]["key"] if st.get("beam") else None)              # beam_search: the step picks with gar_beam_step, buffers by (K, M, T)
         g = self._graphs.get(gkey)
         if g is None:

@@ -794,6 +794,25 @@ def logits_process_rows(logits, V, out_tokens, step_dev, eos_ids, row_params):
     check(lib(logits.dtype).gar_logits_process_rows(*head, ptr(row_params), row_params.shape[1], stream()), "gar_logits_process_rows")
 
 
+CONSTRAINT_HEADER = 4                # gar_constrain: words of the trie block in front of its arrays
+CONSTRAINT_WORDS = 65536             # capacity of the trie block a state keeps (int32 words), see constrained.py
+CONSTRAINT_DEAD = -1                 # node of a history that is no prefix of any phrase
+
+
+def constrain(logits, V, out_tokens, step_dev, eos_ids, trie, nodes):
+    """``gar_constrain``: the phrase constraint's mask on the rows of ``logits`` [B, ld] in place — -inf everywhere but at the
+    tokens that keep row b's history ``out_tokens[b, :step_dev[0]]`` a prefix of one of its phrases (and at the eos ids behind a
+    complete phrase, or alone when the history is no prefix). ``trie``: the int32 device block laid out by
+    :meth:`PhraseConstraint.pack`; ``nodes`` int32 [B, >= cols + 1] (row-strided view allowed): column 0 holds the rows' roots,
+    the launch at step t >= 1 writes column t. ``step_dev`` None = step 0, ``out_tokens`` None = no history."""
+    B = logits.shape[0]
+    assert trie.dtype == torch.int32 and trie.is_contiguous() and trie.numel() >= CONSTRAINT_HEADER
+    head = _logits_process_args(logits, V, out_tokens, step_dev, eos_ids)
+    assert nodes.dtype == torch.int32 and nodes.dim() == 2 and nodes.shape[0] == B and nodes.shape[1] >= head[7] + 1 and \
+        (nodes.shape[1] <= 1 or nodes.stride(1) == 1)
+    check(lib(logits.dtype).gar_constrain(*head, ptr(trie), trie.numel(), ptr(nodes), nodes.stride(0), stream()), "gar_constrain")
+
+
 def input_check(input_ids, vocab: int, counts, n_rows: int, spans, span_len: int, has_box, flags, attn_mask=None):
     """device-side input checks of generate(validate=False): ORs INPUT_* bits into ``flags`` (int32 [1]). ``attn_mask``: bool /
     uint8 [B, S] generation mask; a row that is not left-padded sets INPUT_MASK_NOT_LEFT_PADDED."""

@@ -583,6 +583,34 @@ int gar_logits_process_rows(int dtype, void* logits, int64_t ld, int B, int V, c
                             int out_cols, const int32_t* step_dev, const int64_t* eos_ids, int n_eos,
                             const int32_t* row_params /* device int32 [B][row_words] */, int row_words, gar_stream_t stream);
 
+/* ---- Phrase-constrained decoding (GARModel.generate(constraint=PhraseConstraint(...))) -----------------------------------------------
+ * Additive: one entry point, GAR_ABI_VERSION stays 16. HF's PrefixConstrainedLogitsProcessor (scores + mask, mask 0 at the allowed
+ * ids and -inf elsewhere) for the callback "the row's generated tokens remain a prefix of one of its prompt's phrases", the phrases
+ * held on the device as a token trie. As the reference calls generate(inputs_embeds=...) without input_ids, the history of row b
+ * is its generated tokens: out_tokens[b * out_stride + 0 .. t - 1], t = step_dev[0] (NULL = 0) clamped to [0, out_cols];
+ * out_tokens NULL = step 0. Edits logits [B, ld] (f32 / the library's 16-bit type) in place, behind gar_logits_process and in front
+ * of gar_topk_lp / gar_sample / gar_argmax.
+ * trie: device int32 [trie_words], read on every launch, so one captured graph serves any phrase set:
+ *   [0] n_nodes  [1] n_edges  [2] n_rows  [3] 0, then root[n_rows] (the root node of every row's prompt: the caller fills column 0 of
+ *   the node plane from it), first[n_nodes + 1] (CSR: the edges of node i are first[i] .. first[i + 1] - 1), tok[n_edges] (ascending
+ *   within a node), child[n_edges], and one terminal bit per node in (n_nodes + 31) / 32 words (bit i & 31 of word i >> 5).
+ * nodes: int32 [B][node_stride], node_stride >= out_cols + 1, owned by the request: nodes[b][t] is the row's node before step t,
+ *   DEAD = -1 when its history is no prefix of any phrase. Column 0 is the caller's; a launch at step t >= 1 computes column t from
+ *   column t - 1 and out_tokens[b][t - 1] by a binary search among the node's children and stores it. It reads nothing else of the
+ *   plane, so a second launch at the same step rewrites the same value and leaves the same logits (idempotent).
+ * Allowed at step t: the tokens of the node's edges; every eos id (eos_ids int64 [n_eos], entries outside [0, V) never match) as
+ *   well when the node is terminal; exactly the eos ids when the node is DEAD. Every other entry of columns 0 .. V - 1 becomes -inf.
+ * Contract: ONE launch per step, one 1024-thread workgroup per row, one vocabulary bitmap in LDS (V <= gar_logits_process_max_vocab()),
+ * no global atomics, no allocation, no synchronisation, hipGraph-capturable, deterministic. The row is swept in 16-byte pieces for
+ * any ld >= V and any element-aligned base: a piece without an allowed id is stored without being loaded, a piece of allowed ids is
+ * not touched. Allowed entries and columns V..ld-1 keep their bytes. Every index is checked before use — the block's sizes
+ * against trie_words, a node against n_nodes, an edge range against n_edges, a token id against V, t against out_cols; what fails
+ * names DEAD and is never followed, so an inconsistent block yields eos-only rows. Rows whose eos latch is set are masked like
+ * any other. NaN logits are unspecified. */
+int gar_constrain(int dtype, void* logits, int64_t ld, int B, int V, const int64_t* out_tokens, int64_t out_stride, int out_cols,
+                  const int32_t* step_dev, const int64_t* eos_ids, int n_eos, const int32_t* trie, int trie_words, int32_t* nodes,
+                  int64_t node_stride, gar_stream_t stream);
+
 /* ---- Per-row requests in one batch (ContinuousBatcher(sampling=True)) ----------------------------------------------------------------
  * Additive: one entry point beside gar_sample / gar_argmax, whose signatures and results stand, so GAR_ABI_VERSION stays 16. The rows
  * of one launch belong to different requests: row b picks its token under row_words[b] — device int32 [B][8], read on every launch,
